@@ -16,12 +16,17 @@ headline number is quoted on: 720 steps in 371.7 s = 1.94 steps/s, README.md:52)
                          are proven as `--segments S` (default 3) contiguous row segments folded concurrently on the GPU and merged
                          into one object (vimz_ivc_merge: out-of-circuit NIFS on both curves); the segments' start states
                          (hash-only chains), the merges and, at N > 1, rank 0's final fold of the ranks' merged proofs are inside the
-                         timed region.  The object is verified for exactly (world x K steps, z0) and compressed.  `--segments 1`:
-                         one IVC chain.  A second proof of K rows with per-kernel HIP events gives the roofline figure.
+                         timed region.  `--segments 1`: one IVC chain.
   --mode accumulator     the NIFS accumulator over the step circuit's own instances (vimz_prover_*): row segments fold
                          independently and are merged by a host-side final fold (BASELINE.json north_star's sharding picture).
 N > 1: every rank folds its own rows (independent row-folds, weak scaling, no data-path collective).  Prints ONE JSON line on
 rank 0.
+
+A plain run sets up, warms up, times ONE pass of exactly K rows (`--repeats R`: R passes, `value` from the median one), writes the
+outputs if asked to (`--dump-outputs DIR`) and prints the line.  `--full` adds everything else: seven timed passes by default, every
+proof verified for exactly (world x K steps, z0), the object compressed (CompressedSNARK), a second proof of K rows with per-kernel HIP
+events for the roofline figure, the isolated kernel timings, the one-chain / host-head-batch / Sonobe-backend extras, the host
+fingerprint and the CPU baseline (`--no-compress`, `--no-extras`, `--no-cpu-baseline` drop parts of it).
 """
 import argparse
 import json
@@ -194,6 +199,47 @@ def _ints(limbs):
     return [int(a[0]) | int(a[1]) << 64 | int(a[2]) << 128 | int(a[3]) << 192 for a in limbs]
 
 
+DUMP_SAMPLE = 1 << 16      # elements kept of a longer vector by --dump-outputs (a fixed, seeded sample)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array of uint64 words as out_dir/<name>.npy in float64, each word as its two 32-bit halves (low first),
+    so that the values are exact: a field element (4 x u64, canonical, little-endian) becomes eight limbs.  A vector of more than
+    DUMP_SAMPLE elements is cut to a sample of that many at indices drawn with a fixed seed (the same for the same length), written
+    beside it as <name>_index.npy.  The witness vectors are sampled; the commitments to them are written whole."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        if a.ndim == 2 and a.shape[0] > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(a.shape[0], DUMP_SAMPLE, replace=False))
+            np.save(os.path.join(out_dir, f"{name}_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+        halves = np.stack([a & np.uint64(0xFFFFFFFF), a >> np.uint64(32)], axis=-1).reshape(a.shape[:-1] + (-1,))
+        np.save(os.path.join(out_dir, f"{name}.npy"), halves.astype(np.float64))
+
+
+def merged_proof_outputs(proof):
+    """What a caller of the IVC path receives: the ONE merged proof object — its final state, the running instances and witness
+    vectors of both curves, and the statement records an independent verifier replays."""
+    from vimz_amd import hip
+    _, z_end, steps = proof.state()
+    z = np.array([[(v >> (64 * k)) & 0xFFFFFFFFFFFFFFFF for k in range(4)] for v in z_end], dtype=np.uint64)
+    out = {"final_state": z, "steps": np.array([steps], dtype=np.uint64), "records": proof.records()}
+    for side, tag in ((0, "primary"), (1, "secondary")):
+        out[f"{tag}_instance"] = proof.export(side, hip.IX_INSTANCE)
+        out[f"{tag}_running_z"] = proof.export(side, hip.IX_RUNNING_Z)
+        out[f"{tag}_running_e"] = proof.export(side, hip.IX_RUNNING_E)
+    return out
+
+
+def accumulator_outputs(prover):
+    """What a caller of the accumulator path receives: the merged prover's running instance and its witness and error vectors."""
+    inst = prover.instance()
+    Z, E = prover.running()
+    return {"final_state": inst["z"], "steps": np.array([inst["steps"]], dtype=np.uint64), "comm_w": inst["comm_W"].reshape(-1, 4),
+            "comm_e": inst["comm_E"].reshape(-1, 4), "u": inst["u"].reshape(-1, 4), "running_z": Z, "running_e": E}
+
+
 def _kernel_source_sha():
     """sha256[:16] of the MSM kernels' source: profiles/pmc_traffic.json records it with every entry, so a counter figure measured on
     other kernel code is flagged stale instead of being quoted as current."""
@@ -273,7 +319,7 @@ def main_ivc(args, rank, world, dist, torch, ctxs, circuit, params, steps_all, g
             pw = prove(rows_warm, z0)
         if pw is not None:
             pw.close()
-    # The timed job, R times (--repeats, default 7): each pass is ONE proof of world x K rows from z0 (proof sets: every rank its own proof of
+    # The timed job, R times (--repeats, default 1; 7 with --full): each pass is ONE proof of world x K rows from z0 (proof sets: every rank its own proof of
     # K rows), bracketed by barrier + synchronise on both sides; `value` is computed from the MEDIAN pass, every pass's time is printed.
     # Rank r's rows start at the state after the r·K rows of the ranks before it: rank 0 runs that hash-only chain once and hands every
     # rank its start state; the ranks' merged proofs go to rank 0 through node-local shared memory and are folded in row order.
@@ -303,9 +349,9 @@ def main_ivc(args, rank, world, dist, torch, ctxs, circuit, params, steps_all, g
             t = torch.tensor([dt], dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t[0])
-        # acceptance of every pass: its ONE object verifies for exactly (world x K steps, z0)   [proof sets: every rank's own proof for (K, z0)]
+        # (--full) acceptance of every pass: its ONE object verifies for exactly (world x K steps, z0)   [proof sets: every rank's own proof for (K, z0)]
         code = None
-        if proof is not None:
+        if args.full and proof is not None:
             n_claim = K if (args.proof_set or world == 1) else world * K
             code = proof.verify(n_claim, z0)
         passes.append({"dt": dt, "host_cpu_s": host_cpu_s, "tm": tm, "t0": t0, "verify_code": code, "prof": [ivc.profile() for ivc in ivcs]})
@@ -336,10 +382,12 @@ def main_ivc(args, rank, world, dist, torch, ctxs, circuit, params, steps_all, g
     t_fold = dt - final_tail_s
     timed_rows = K
     timed_total = K * world
-    # acceptance: the ONE object verifies for exactly (world x K steps, z0)   [proof sets: every rank's own proof for (K, z0)]
+    if args.dump_outputs and rank == 0 and proof is not None:      # what the last timed pass computed, before anything else touches it
+        dump_outputs(args.dump_outputs, merged_proof_outputs(proof))
+    # (--full) acceptance: the ONE object verifies for exactly (world x K steps, z0)   [proof sets: every rank's own proof for (K, z0)]
     t_v = time.time()
     ok, codes = True, []
-    if proof is not None:
+    if args.full and proof is not None:
         n_claim = K if (args.proof_set or world == 1) else world * K
         code = proof.verify(n_claim, z0)
         codes = [code]
@@ -347,9 +395,9 @@ def main_ivc(args, rank, world, dist, torch, ctxs, circuit, params, steps_all, g
     verify_s = time.time() - t_v
     merged_info = proof.info() if proof is not None else None
     merge_prof = proof.profile() if proof is not None else None
-    # CompressedSNARK::prove / verify of the merged proof (mod.rs:52-67; README.md:196 counts it into the total proof time)
+    # (--full) CompressedSNARK::prove / verify of the merged proof (mod.rs:52-67; README.md:196 counts it into the total proof time)
     compress = None
-    if rank == 0 and proof is not None and not args.no_compress:
+    if args.full and rank == 0 and proof is not None and not args.no_compress:
         try:
             blob, tc = proof.compress()
             t_cv = time.time()
@@ -361,161 +409,32 @@ def main_ivc(args, rank, world, dist, torch, ctxs, circuit, params, steps_all, g
             print(f"[bench] compression skipped: {e}", file=sys.stderr)
     if proof is not None:
         proof.close()
-    # second pass, outside the timed region: the same K rows proven again with HIP events around every kernel of the primary MSM(T)
-    # launches on the stream they run on -> the roofline figure
-    for c in ctxs:
-        c.set_profiling(True)
-        c.msm_profile_totals(reset=True)
-    t1 = time.time()
-    p2 = prove(rows_prof if len(rows_prof) == K else rows_timed, z0)
-    for c in ctxs:
-        c.sync()
-    dt_prof = time.time() - t1
-    p2.close()
-    tots = [c.msm_profile_totals() for c in ctxs]
-    tot = {"ms": {k: sum(t["ms"][k] for t in tots) for k in tots[0]["ms"]}, "calls": sum(t["calls"] for t in tots),
-           "points": sum(t["points"] for t in tots), "entries": sum(t["entries"] for t in tots)}
-    for c in ctxs:
-        c.set_profiling(False)
-    if dist is not None:
-        t = torch.tensor([1 if ok else 0], dtype=torch.int64)
-        dist.all_reduce(t, op=dist.ReduceOp.MIN)
-        ok = bool(int(t[0]))
+    if args.full:
+        # second pass, outside the timed region: the same K rows proven again with HIP events around every kernel of the primary MSM(T)
+        # launches on the stream they run on -> the roofline figure
+        for c in ctxs:
+            c.set_profiling(True)
+            c.msm_profile_totals(reset=True)
+        t1 = time.time()
+        p2 = prove(rows_prof if len(rows_prof) == K else rows_timed, z0)
+        for c in ctxs:
+            c.sync()
+        dt_prof = time.time() - t1
+        p2.close()
+        tots = [c.msm_profile_totals() for c in ctxs]
+        tot = {"ms": {k: sum(t["ms"][k] for t in tots) for k in tots[0]["ms"]}, "calls": sum(t["calls"] for t in tots),
+               "points": sum(t["points"] for t in tots), "entries": sum(t["entries"] for t in tots)}
+        for c in ctxs:
+            c.set_profiling(False)
+        if dist is not None:
+            t = torch.tensor([1 if ok else 0], dtype=torch.int64)
+            dist.all_reduce(t, op=dist.ReduceOp.MIN)
+            ok = bool(int(t[0]))
     if rank == 0:
         info = ivcs[0].info()
         n_w, n_c, nnz = info["primary_wires"], info["primary_constraints"], info["primary_nnz"]
-        calls = max(1, tot["calls"])
-        acc_ms = tot["ms"]["accumulate"] / calls
-        msm_ms = sum(tot["ms"].values()) / calls
-        alg_bytes = 96.0 * tot["points"] / calls       # 32 B scalar + 64 B base per point of the launch
-        achieved = alg_bytes / (acc_ms * 1e-3) / 1e9 if acc_ms else 0.0
-        adds = tot["entries"] / calls
-        # for reference: the same kernel over the same kind of data (the running error vector of the first segment's proof, which has
-        # the cross terms' zero and repetition structure) with nothing else on the GPU
-        alone_ms = None
-        try:
-            E = np.ascontiguousarray(ivcs[0].export(0, hip.IX_RUNNING_E))[:info["step_constraints"]]
-            vec = ctxs[0].vec_from_host(_lib.FIELD_BN254_FR, E)
-            ctxs[0].set_profiling(True)
-            ms = []
-            for _ in range(7):
-                ctxs[0].msm_vec(params.ck, vec)
-                ms.append(ctxs[0].msm_last_profile()["ms"]["accumulate"])
-            ctxs[0].set_profiling(False)
-            vec.free()
-            alone_ms = sorted(ms[1:])[len(ms[1:]) // 2]
-        except Exception as e:                          # informational only
-            print(f"[bench] isolated k_accum measurement skipped: {e}", file=sys.stderr)
-        # the kernel on a step's CRITICAL chain: the fused small MSM (four per step over the verifier circuits' 7.7 k wires / rows),
-        # alone on the GPU over dense scalars of that size (in a fold it runs under the bulk kernels: profiles/ has the in-bench trace)
-        small = None
-        try:
-            n_s = info["verifier_wires"] - 2
-            rs = np.random.default_rng(5)
-            dense = rs.integers(0, 1 << 63, size=(n_s, 4), dtype=np.uint64); dense[:, 3] &= np.uint64((1 << 60) - 1)
-            vec = ctxs[0].vec_from_host(_lib.FIELD_BN254_FR, dense)
-            ctxs[0].set_profiling(True)
-            ms = []
-            for _ in range(9):
-                ctxs[0].msm_vec(params.ck, vec, base_offset=info["step_wires"] - 1)
-                ms.append(ctxs[0].msm_last_profile()["ms"]["accumulate"])
-            ctxs[0].set_profiling(False)
-            vec.free()
-            sm = sorted(ms[1:])[len(ms[1:]) // 2]
-            k_win = 37
-            small = {"kernel": "k_msm_small (one launch: digits, LDS counting sort, sub-bucket sums, segment tree, chunk merge, weighted bucket reduction)",
-                     "points": n_s, "windows": k_win, "algorithmic_bytes_per_launch": 96.0 * n_s, "kernel_ms_alone_on_gpu": sm,
-                     "achieved": 96.0 * n_s / (sm * 1e-3) / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": 96.0 * n_s / (sm * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-                     "bucket_additions": n_s * k_win, "int_utilisation": n_s * k_win / (sm * 1e-3) / 1e9 / MIXED_ADD_PEAK_GOPS,
-                     "bound": "latency: 6 dependent mixed additions, then 19 four-lane levels of dependent additions at ~3.6 us on one wave per SIMD (DESIGN.md §4, §9c); four launches per step, two of them in series"}
-        except Exception as e:
-            print(f"[bench] isolated k_msm_small measurement skipped: {e}", file=sys.stderr)
-        traffic, traffic_src, traffic_stale = _pmc_traffic(f"{args.transformation}_step_{args.resolution}_ivc")
         n_w2, n_c2, nnz2 = info["secondary_wires"], info["secondary_constraints"], info["secondary_nnz"]
-        step_bytes = sum(96 * w + 96 * c + 8 * z + 32 * w + 96 * c + 7 * 32 * c + 3 * 32 * w + 12 * 32 * c for w, c, z in ((n_w, n_c, nnz), (n_w2, n_c2, nnz2)))
         phases = {k: 1e3 * sum(p1[k][0] for p1 in prof1) / max(1, timed_rows) for k in prof1[0]}      # (reset() at the start of the timed proof zeroed the counters)
-        # extra (N = 1): the same K rows as ONE chain (one IVC, no segments, no merge) — what a single sequential prove_step loop reaches
-        one_chain = None
-        if world == 1 and S > 1 and not args.no_extras:
-            # a chain of its OWN — a context and a prover made for it, the way `--segments 1` runs — not one of the three segments' provers: the streams of
-            # provers that were created side by side are interleaved over the hardware queues, which suits the three-segment schedule (+5 %) and costs a lone
-            # chain 8 % (profiles/r05_setup_ab.txt)
-            c1 = iv1 = None
-            try:
-                c1 = hip.Context(ctxs[0].device)
-                iv1 = hip.IVC(c1, circuit, params.ck, ck2, max_batch=args.batch)
-                ds = []
-                for rep in range(4):      # the first pass warms the prover's buffers and thread pools
-                    iv1.reset(z0)
-                    c1.sync()
-                    t3 = time.time()
-                    iv1.fold(rows_timed)
-                    c1.sync()
-                    if rep:
-                        ds.append(time.time() - t3)
-                one_chain = {"steps_per_s": K / sorted(ds)[len(ds) // 2], "samples_steps_per_s": [K / d for d in ds], "verified": iv1.verify(K, z0) == 0,
-                             "note": "the same rows as ONE IVC chain on a prover of its own (what bench.py --segments 1 measures); median of three passes"}
-            except Exception as e:
-                print(f"[bench] one-chain extra skipped: {e}", file=sys.stderr)
-            finally:
-                if iv1 is not None:
-                    iv1.close()
-                if c1 is not None:
-                    c1.close()
-        # extra (N = 1): the same timed passes under the library's DEFAULT policy for short calls — the first rows' Poseidon chains on a host pool (a hybrid:
-        # only proofs of <= 28 rows take it) — where `value` was measured with every row's witness on the GPU
-        all_hip = None
-        if world == 1 and not args.no_extras and not args.host_head_batch:
-            try:
-                hip.set_head_rows(-1)
-                if hip.head_rows_policy(K, segments=S > 1) > 0:
-                    pw = prove(rows_timed, z0); pw.close()      # (first use of this schedule's buffers)
-                    ds = []
-                    for _ in range(R):
-                        sync_all()
-                        t4 = time.time()
-                        pa = prove(rows_timed, z0)
-                        sync_all()
-                        ds.append(time.time() - t4)
-                        ok_a = pa.verify(K, z0) == 0
-                        pa.close()
-                    all_hip = {"steps_per_s": K / sorted(ds)[R // 2], "samples_steps_per_s": [K / d for d in ds], "verified": bool(ok_a), "head_rows": int(ivcs[0].info().get("head_rows", -1)),
-                               "note": "the same passes with the library's default policy (vimz_set_head_rows(-1)): a proof this short has its rows' Poseidon chains evaluated on a host "
-                                       "pool while the GPU does the rest — a hybrid no whole image takes; `value` is the all-HIP schedule"}
-            except Exception as e:
-                print(f"[bench] host-head-batch extra skipped: {e}", file=sys.stderr)
-            finally:
-                hip.set_head_rows(0)
-        # extra (N = 1): the reference's second backend on the same image — Nova + CycleFold (vimz_cf_*): the whole image as one
-        # chain and as ONE merged proof of S concurrent segments (vimz_cf_merge), each in a process of its own the way `vimz -b sonobe` would run
-        # (tools/e2e.py; a child process, started the ordinary way — this one keeps its GPU state)
-        sonobe = None
-        if world == 1 and not args.no_extras and not args.proof_set and args.resolution == "HD":
-            try:
-                import subprocess
-                runs = {}
-                for segs in sorted({1, S}):
-                    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "e2e.py"), args.transformation, args.resolution, str(segs), "cyclefold"],
-                                       cwd=ROOT, capture_output=True, text=True, timeout=600)
-                    line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
-                    if r.returncode != 0 or not line:
-                        raise RuntimeError(f"tools/e2e.py exited with {r.returncode}: {r.stderr[-300:]}")
-                    runs[segs] = json.loads(line[-1])
-                one = runs[1]
-                sonobe = {"one_chain_steps_per_s": one["steps_per_s"], "steps": one["steps"], "verified": bool(one["verified"]), "fold_s": one["spans_s"]["Fold input"],
-                          "main_constraints": one["info"]["main_constraints"], "cyclefold_constraints": one["info"]["cyclefold_constraints"],
-                          "one_chain_ms_per_step": one["ms_per_step_first_segment"], "decider": one.get("decider"),
-                          "note": "Nova + CycleFold IVC (the Sonobe backend's prove_step loop, vimz/src/sonobe_backend/folding.rs:52-66) over the whole image, same kernels; own process"}
-                if S > 1:
-                    mg = runs[S]
-                    sonobe.update({"merged_steps_per_s": mg["steps_per_s"], "segments": S, "merged_verified": bool(mg["verified"]), "merged_fold_s": mg["spans_s"]["Fold input"],
-                                   "state_chain_s": mg["state_chain_s"], "merge_s": mg["merge_s"]})
-            except Exception as e:
-                print(f"[bench] sonobe-backend extra skipped: {e}", file=sys.stderr)
-        try:
-            fingerprint = ctxs[0].host_fingerprint()
-        except Exception as e:                          # informational only
-            fingerprint = {"error": str(e)}
         head_rows = int(info.get("head_rows", -1)) if isinstance(info, dict) else -1
         out = {
             "metric": "nova_folding_steps_per_sec",
@@ -538,17 +457,14 @@ def main_ivc(args, rank, world, dist, torch, ctxs, circuit, params, steps_all, g
                                        (f"ONE proof object: {S} contiguous row segments per GPU folded concurrently as Nova IVCs and merged (vimz_ivc_merge)" if S > 1 else "one IVC chain per GPU") +
                                        ("" if world == 1 else f"; {world} GPUs prove {world} contiguous runs of rows, rank 0 folds their merged proofs into ONE object (host-side sequential final fold); no data-path collective"))},
             "timed_passes": R,
-            "value_is": f"median of {R} timed passes of exactly {timed_rows} rows per GPU, each ONE proof from z0 bracketed by barrier + synchronise; every pass's proof verified",
+            "value_is": ("one timed pass" if R == 1 else f"median of {R} timed passes") + f" of exactly {timed_rows} rows per GPU, each ONE proof from z0 bracketed by barrier + synchronise"
+                        + ("; every pass's proof verified" if args.full else ""),
             "samples_ms_per_step": samples_ms, "samples_steps_per_s": [timed_total / (m * 1e-3 * max(1, timed_rows)) for m in samples_ms],
             "samples_min_max_steps_per_s": [timed_total / (max(samples_ms) * 1e-3 * max(1, timed_rows)), timed_total / (min(samples_ms) * 1e-3 * max(1, timed_rows))],
             "samples_spread_pct": 100.0 * (max(samples_ms) - min(samples_ms)) / (sorted(samples_ms)[len(samples_ms) // 2]),
             "head_rows": head_rows,
-            "host_fingerprint": fingerprint,
-            "verified": bool(ok),
-            "verify_codes": codes,
             "proof_object": merged_info,
             "folded_steps_total": merged_info["steps"] if merged_info else None,
-            "verify_s": verify_s,
             "state_chain_s": state_chain_s,
             "merge_s": tm.get("merge_s", 0.0),
             "final_fold_s": final_tail_s if world > 1 else 0.0,
@@ -562,39 +478,176 @@ def main_ivc(args, rank, world, dist, torch, ctxs, circuit, params, steps_all, g
             "host_cpu": {"core_seconds_rank0": host_cpu_s, "cores_busy_rank0": host_cpu_s / dt, "core_ms_per_step_rank0": 1e3 * host_cpu_s / max(1, K),
                          "note": "process CPU time (all threads: folding threads, helpers, issuers, pools, HIP runtime) of rank 0 inside the timed region"},
             "merge_profile_s": merge_prof,
-            "one_chain": one_chain,
-            "host_head_batch_schedule": all_hip,
-            "sonobe_backend": sonobe,
-            "compressed_snark": compress,
             "end_to_end_estimate_s": {"keygen_and_setup": setup_s, "setup_split": getattr(args, "setup_split", None), "fold_720_steps_one_gpu": 720 * dt / max(1, timed_total),
                                       "compress": (compress["setup_s"] + compress["prove_s"]) if compress else None,
                                       "total_720_steps": (setup_s + 720 * dt / max(1, timed_total) + compress["setup_s"] + compress["prove_s"]) if compress else None,
                                       "reference_cpu_server": {"keygen_s": 6.5, "fold_s": 371.7, "compress_s_sample_run": 13.0, "source": "README.md:52, sample-output.png"}},
             "published_reference": {"contrast_HD_steps_per_s_cpu_server": 1.94, "source": "README.md:52 (720 steps / 371.7 s)"},
             "phase_ms_per_step_per_proof": phases,
-            "roofline_critical_chain_kernel": small,
-            "roofline": {"bound": "hbm", "kernel": "k_accum (bucket accumulation) of the primary MSM(T) launches over the step circuit's rows",
-                         "measured": f"HIP events on the kernel's own stream over a second proof of {timed_rows} rows made the same way right after the timed region (events off while `value` is timed); that pass ran at {timed_rows / dt_prof:.1f} steps/s",
-                         "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
-                         "traffic": traffic, "traffic_source": traffic_src, "traffic_stale": traffic_stale,
-                         "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms": acc_ms, "launches": tot["calls"], "msm_gpu_ms": msm_ms,
-                         "mixed_adds_per_launch": adds, "msm_phase_ms": {k: v / calls for k, v in tot["ms"].items()},
-                         "int_utilisation": (adds / (acc_ms * 1e-3) / 1e9 / MIXED_ADD_PEAK_GOPS) if acc_ms else 0.0,
-                         "kernel_ms_alone_on_gpu": alone_ms,
-                         "frac_alone_on_gpu": (alg_bytes / (alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS) if alone_ms else None,
-                         "step_algorithmic_bytes": step_bytes, "step_hbm_frac": step_bytes / (dt / max(1, timed_rows)) / 1e9 / HBM_PEAK_GBPS},
         }
-        if not args.no_cpu_baseline and world == 1:      # the CPU baseline is timed at N = 1 only
-            cores = usable_cores()
-            ck_host = params.ck.download(0, info["primary_constraints"] + 8)
-            ck2_host = ck2.download(0, max(info["secondary_wires"], info["secondary_constraints"]))
-            sps, secs, n_cpu, cph = cpu_baseline(circuit, mine, z0, ck_host, args.cpu_seconds, cores, ivc=ivcs[0], ck2_host=ck2_host)
-            out["cpu_baseline"] = {"value": sps, "unit": "steps/s", "cores": cores, "kind": "port",
-                                   "sample": f"{n_cpu} folding steps with the CPU oracle (C++ restatement; not the Rust binary), like for like with a GPU step: per row the step circuit's witness "
-                                             f"(rows of a batch side by side on the host threads), (A,B,C)·z, MSM(W), cross term, MSM(T) and folds of the primary instance, plus the two verifier "
-                                             f"circuits' share — their (A,B,C)·z, four commitments, cross terms, folds and the hashes / scalar multiplications of their witness generation; "
-                                             f"std::thread over the usable cores (affinity and cgroup quota), {secs:.1f} s",
-                                   "seconds_per_step_by_phase": cph}
+        if args.full:
+            calls = max(1, tot["calls"])
+            acc_ms = tot["ms"]["accumulate"] / calls
+            msm_ms = sum(tot["ms"].values()) / calls
+            alg_bytes = 96.0 * tot["points"] / calls       # 32 B scalar + 64 B base per point of the launch
+            achieved = alg_bytes / (acc_ms * 1e-3) / 1e9 if acc_ms else 0.0
+            adds = tot["entries"] / calls
+            # for reference: the same kernel over the same kind of data (the running error vector of the first segment's proof, which has
+            # the cross terms' zero and repetition structure) with nothing else on the GPU
+            alone_ms = None
+            try:
+                E = np.ascontiguousarray(ivcs[0].export(0, hip.IX_RUNNING_E))[:info["step_constraints"]]
+                vec = ctxs[0].vec_from_host(_lib.FIELD_BN254_FR, E)
+                ctxs[0].set_profiling(True)
+                ms = []
+                for _ in range(7):
+                    ctxs[0].msm_vec(params.ck, vec)
+                    ms.append(ctxs[0].msm_last_profile()["ms"]["accumulate"])
+                ctxs[0].set_profiling(False)
+                vec.free()
+                alone_ms = sorted(ms[1:])[len(ms[1:]) // 2]
+            except Exception as e:                          # informational only
+                print(f"[bench] isolated k_accum measurement skipped: {e}", file=sys.stderr)
+            # the kernel on a step's CRITICAL chain: the fused small MSM (four per step over the verifier circuits' 7.7 k wires / rows),
+            # alone on the GPU over dense scalars of that size (in a fold it runs under the bulk kernels: profiles/ has the in-bench trace)
+            small = None
+            try:
+                n_s = info["verifier_wires"] - 2
+                rs = np.random.default_rng(5)
+                dense = rs.integers(0, 1 << 63, size=(n_s, 4), dtype=np.uint64); dense[:, 3] &= np.uint64((1 << 60) - 1)
+                vec = ctxs[0].vec_from_host(_lib.FIELD_BN254_FR, dense)
+                ctxs[0].set_profiling(True)
+                ms = []
+                for _ in range(9):
+                    ctxs[0].msm_vec(params.ck, vec, base_offset=info["step_wires"] - 1)
+                    ms.append(ctxs[0].msm_last_profile()["ms"]["accumulate"])
+                ctxs[0].set_profiling(False)
+                vec.free()
+                sm = sorted(ms[1:])[len(ms[1:]) // 2]
+                k_win = 37
+                small = {"kernel": "k_msm_small (one launch: digits, LDS counting sort, sub-bucket sums, segment tree, chunk merge, weighted bucket reduction)",
+                         "points": n_s, "windows": k_win, "algorithmic_bytes_per_launch": 96.0 * n_s, "kernel_ms_alone_on_gpu": sm,
+                         "achieved": 96.0 * n_s / (sm * 1e-3) / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": 96.0 * n_s / (sm * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                         "bucket_additions": n_s * k_win, "int_utilisation": n_s * k_win / (sm * 1e-3) / 1e9 / MIXED_ADD_PEAK_GOPS,
+                         "bound": "latency: 6 dependent mixed additions, then 19 four-lane levels of dependent additions at ~3.6 us on one wave per SIMD (DESIGN.md §4, §9c); four launches per step, two of them in series"}
+            except Exception as e:
+                print(f"[bench] isolated k_msm_small measurement skipped: {e}", file=sys.stderr)
+            traffic, traffic_src, traffic_stale = _pmc_traffic(f"{args.transformation}_step_{args.resolution}_ivc")
+            step_bytes = sum(96 * w + 96 * c + 8 * z + 32 * w + 96 * c + 7 * 32 * c + 3 * 32 * w + 12 * 32 * c for w, c, z in ((n_w, n_c, nnz), (n_w2, n_c2, nnz2)))
+            # extra (N = 1): the same K rows as ONE chain (one IVC, no segments, no merge) — what a single sequential prove_step loop reaches
+            one_chain = None
+            if world == 1 and S > 1 and not args.no_extras:
+                # a chain of its OWN — a context and a prover made for it, the way `--segments 1` runs — not one of the three segments' provers: the streams of
+                # provers that were created side by side are interleaved over the hardware queues, which suits the three-segment schedule (+5 %) and costs a lone
+                # chain 8 % (profiles/r05_setup_ab.txt)
+                c1 = iv1 = None
+                try:
+                    c1 = hip.Context(ctxs[0].device)
+                    iv1 = hip.IVC(c1, circuit, params.ck, ck2, max_batch=args.batch)
+                    ds = []
+                    for rep in range(4):      # the first pass warms the prover's buffers and thread pools
+                        iv1.reset(z0)
+                        c1.sync()
+                        t3 = time.time()
+                        iv1.fold(rows_timed)
+                        c1.sync()
+                        if rep:
+                            ds.append(time.time() - t3)
+                    one_chain = {"steps_per_s": K / sorted(ds)[len(ds) // 2], "samples_steps_per_s": [K / d for d in ds], "verified": iv1.verify(K, z0) == 0,
+                                 "note": "the same rows as ONE IVC chain on a prover of its own (what bench.py --segments 1 measures); median of three passes"}
+                except Exception as e:
+                    print(f"[bench] one-chain extra skipped: {e}", file=sys.stderr)
+                finally:
+                    if iv1 is not None:
+                        iv1.close()
+                    if c1 is not None:
+                        c1.close()
+            # extra (N = 1): the same timed passes under the library's DEFAULT policy for short calls — the first rows' Poseidon chains on a host pool (a hybrid:
+            # only proofs of <= 28 rows take it) — where `value` was measured with every row's witness on the GPU
+            all_hip = None
+            if world == 1 and not args.no_extras and not args.host_head_batch:
+                try:
+                    hip.set_head_rows(-1)
+                    if hip.head_rows_policy(K, segments=S > 1) > 0:
+                        pw = prove(rows_timed, z0); pw.close()      # (first use of this schedule's buffers)
+                        ds = []
+                        for _ in range(R):
+                            sync_all()
+                            t4 = time.time()
+                            pa = prove(rows_timed, z0)
+                            sync_all()
+                            ds.append(time.time() - t4)
+                            ok_a = pa.verify(K, z0) == 0
+                            pa.close()
+                        all_hip = {"steps_per_s": K / sorted(ds)[R // 2], "samples_steps_per_s": [K / d for d in ds], "verified": bool(ok_a), "head_rows": int(ivcs[0].info().get("head_rows", -1)),
+                                   "note": "the same passes with the library's default policy (vimz_set_head_rows(-1)): a proof this short has its rows' Poseidon chains evaluated on a host "
+                                           "pool while the GPU does the rest — a hybrid no whole image takes; `value` is the all-HIP schedule"}
+                except Exception as e:
+                    print(f"[bench] host-head-batch extra skipped: {e}", file=sys.stderr)
+                finally:
+                    hip.set_head_rows(0)
+            # extra (N = 1): the reference's second backend on the same image — Nova + CycleFold (vimz_cf_*): the whole image as one
+            # chain and as ONE merged proof of S concurrent segments (vimz_cf_merge), each in a process of its own the way `vimz -b sonobe` would run
+            # (tools/e2e.py; a child process, started the ordinary way — this one keeps its GPU state)
+            sonobe = None
+            if world == 1 and not args.no_extras and not args.proof_set and args.resolution == "HD":
+                try:
+                    import subprocess
+                    runs = {}
+                    for segs in sorted({1, S}):
+                        r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "e2e.py"), args.transformation, args.resolution, str(segs), "cyclefold"],
+                                           cwd=ROOT, capture_output=True, text=True, timeout=600)
+                        line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+                        if r.returncode != 0 or not line:
+                            raise RuntimeError(f"tools/e2e.py exited with {r.returncode}: {r.stderr[-300:]}")
+                        runs[segs] = json.loads(line[-1])
+                    one = runs[1]
+                    sonobe = {"one_chain_steps_per_s": one["steps_per_s"], "steps": one["steps"], "verified": bool(one["verified"]), "fold_s": one["spans_s"]["Fold input"],
+                              "main_constraints": one["info"]["main_constraints"], "cyclefold_constraints": one["info"]["cyclefold_constraints"],
+                              "one_chain_ms_per_step": one["ms_per_step_first_segment"], "decider": one.get("decider"),
+                              "note": "Nova + CycleFold IVC (the Sonobe backend's prove_step loop, vimz/src/sonobe_backend/folding.rs:52-66) over the whole image, same kernels; own process"}
+                    if S > 1:
+                        mg = runs[S]
+                        sonobe.update({"merged_steps_per_s": mg["steps_per_s"], "segments": S, "merged_verified": bool(mg["verified"]), "merged_fold_s": mg["spans_s"]["Fold input"],
+                                       "state_chain_s": mg["state_chain_s"], "merge_s": mg["merge_s"]})
+                except Exception as e:
+                    print(f"[bench] sonobe-backend extra skipped: {e}", file=sys.stderr)
+            try:
+                fingerprint = ctxs[0].host_fingerprint()
+            except Exception as e:                          # informational only
+                fingerprint = {"error": str(e)}
+            out.update({
+                "host_fingerprint": fingerprint,
+                "verified": bool(ok),
+                "verify_codes": codes,
+                "verify_s": verify_s,
+                "one_chain": one_chain,
+                "host_head_batch_schedule": all_hip,
+                "sonobe_backend": sonobe,
+                "compressed_snark": compress,
+                "roofline_critical_chain_kernel": small,
+                "roofline": {"bound": "hbm", "kernel": "k_accum (bucket accumulation) of the primary MSM(T) launches over the step circuit's rows",
+                             "measured": f"HIP events on the kernel's own stream over a second proof of {timed_rows} rows made the same way right after the timed region (events off while `value` is timed); that pass ran at {timed_rows / dt_prof:.1f} steps/s",
+                             "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
+                             "traffic": traffic, "traffic_source": traffic_src, "traffic_stale": traffic_stale,
+                             "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms": acc_ms, "launches": tot["calls"], "msm_gpu_ms": msm_ms,
+                             "mixed_adds_per_launch": adds, "msm_phase_ms": {k: v / calls for k, v in tot["ms"].items()},
+                             "int_utilisation": (adds / (acc_ms * 1e-3) / 1e9 / MIXED_ADD_PEAK_GOPS) if acc_ms else 0.0,
+                             "kernel_ms_alone_on_gpu": alone_ms,
+                             "frac_alone_on_gpu": (alg_bytes / (alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS) if alone_ms else None,
+                             "step_algorithmic_bytes": step_bytes, "step_hbm_frac": step_bytes / (dt / max(1, timed_rows)) / 1e9 / HBM_PEAK_GBPS},
+            })
+            if not args.no_cpu_baseline and world == 1:      # the CPU baseline is timed at N = 1 only
+                cores = usable_cores()
+                ck_host = params.ck.download(0, info["primary_constraints"] + 8)
+                ck2_host = ck2.download(0, max(info["secondary_wires"], info["secondary_constraints"]))
+                sps, secs, n_cpu, cph = cpu_baseline(circuit, mine, z0, ck_host, args.cpu_seconds, cores, ivc=ivcs[0], ck2_host=ck2_host)
+                out["cpu_baseline"] = {"value": sps, "unit": "steps/s", "cores": cores, "kind": "port",
+                                       "sample": f"{n_cpu} folding steps with the CPU oracle (C++ restatement; not the Rust binary), like for like with a GPU step: per row the step circuit's witness "
+                                                 f"(rows of a batch side by side on the host threads), (A,B,C)·z, MSM(W), cross term, MSM(T) and folds of the primary instance, plus the two verifier "
+                                                 f"circuits' share — their (A,B,C)·z, four commitments, cross terms, folds and the hashes / scalar multiplications of their witness generation; "
+                                                 f"std::thread over the usable cores (affinity and cgroup quota), {secs:.1f} s",
+                                       "seconds_per_step_by_phase": cph}
         print(json.dumps(out), flush=True)
     for v in ivcs:
         v.close()
@@ -640,7 +693,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=256)
-    ap.add_argument("--repeats", type=int, default=7, help="timed passes of exactly --steps rows each (ivc mode); `value` is the median pass")
+    ap.add_argument("--repeats", type=int, default=None, help="timed passes of exactly --steps rows each (ivc mode); `value` is the median pass (default: 1; 7 with --full)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: seven timed passes by default, every proof verified, CompressedSNARK, "
+                    "the roofline pass and the isolated kernel timings, the one-chain / host-head-batch / Sonobe-backend extras, the host fingerprint, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the last timed pass computed (the proof object: state, instances, records, a "
+                    "seeded sample of the witness vectors) as DIR/<name>.npy, exact 32-bit limbs in float64")
     ap.add_argument("--warmup", type=int, default=150,
                     help="untimed rows proven first, the same way (default 150: proofs of more than 28 rows take the library's long-call "
                          "schedule - no host-evaluated head batch - and a 32-row warm-up left that path's first use inside the timed region)")
@@ -649,11 +706,11 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="rows whose witnesses are generated together (0: folding.default_batch = 64: every BASELINE configuration below 64 GB of device memory, profiles/r05_batch_sweep.txt)")
     ap.add_argument("--segments", type=int, default=0, help="row segments folded concurrently on each GPU, own context + streams each, and merged into one proof (default in IVC mode: 3, 4 for 192 rows or more per GPU on eight or more host cores, 2 when the rank has fewer than six; 2 accumulators)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--msm-helpers", type=int, default=0, help="IVC mode: split every step's large MSM(T) by base range over this many helper contexts "
                     "(devices after this rank's, wrapping around; on a one-GPU box they share the device): one proof on several GPUs, SURVEY.md §8e")
-    ap.add_argument("--no-compress", action="store_true", help="skip CompressedSNARK::prove / verify of the folded proof")
-    ap.add_argument("--no-extras", action="store_true", help="skip the one-chain and Sonobe-backend extras of the default IVC run")
+    ap.add_argument("--no-compress", action="store_true", help="--full without CompressedSNARK::prove / verify of the folded proof")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the one-chain, host-head-batch and Sonobe-backend extras")
     ap.add_argument("--mode", default="ivc", choices=["ivc", "accumulator"])
     ap.add_argument("--host-head-batch", action="store_true", help="measure `value` under the library's default policy for short calls (first rows' Poseidon chains on a host pool) "
                                                                    "instead of the all-HIP schedule")
@@ -664,6 +721,8 @@ def main():
     ap.add_argument("--cores", type=int, default=0, help="restrict this process (every rank: its own share) to this many host cores before anything starts — "
                     "what a rank has when eight ranks share a 16-core quota (VERDICT r3 #3); 0 = no restriction")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 7 if args.full else 1
 
     if args.gpus < 1:
         ap.error("--gpus must be at least 1")
@@ -775,6 +834,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t[0])
     prof = prover.profile()
+    if args.dump_outputs and rank == 0:      # what the timed fold computed, before the warm-up rows are merged back in
+        dump_outputs(args.dump_outputs, accumulator_outputs(prover))
     if warm_blob is not None:              # put the warm-up rows back in front of the timed ones: one accumulator per rank
         timed_blob = prover.export()
         prover.reset(z_start)
@@ -791,7 +852,7 @@ def main():
             for r in range(1, world):
                 prover.merge(np.frombuffer(gathered[r], dtype=np.uint8))
     final_fold_s = time.time() - t_ff
-    ok = prover.verify() == 0 if (rank == 0 or args.proof_set) else True
+    ok = prover.verify() == 0 if args.full and (rank == 0 or args.proof_set) else True
     if args.proof_set and dist is not None:      # independent proofs: every rank verifies its own; AND them
         t = torch.tensor([1 if ok else 0], dtype=torch.int64)
         dist.all_reduce(t, op=dist.ReduceOp.MIN)
@@ -824,7 +885,6 @@ def main():
             "data": "synthetic: rows of the reference sample image img2.png, contrast factor 1.4" + ("" if args.resolution == "HD" else f", upscaled to {args.resolution}"),
             "config": {"workload": f"{args.transformation}_step_{args.resolution}", "mode": "accumulator", "constraints": n_c, "wires": n_w, "nnz": nnz,
                        "rows_per_rank": args.steps, "segments_per_gpu": S, "witness_batch": args.batch, "parallelism": (f"{world} independent proofs ({args.proof_set}), replicas only" if args.proof_set else f"{world} independent row segments + host final fold")},
-            "verified": bool(ok),
             "folded_steps_total": inst["steps"],
             "final_fold_s": final_fold_s if world > 1 else 0.0,
             "end_to_end_estimate_s": {"keygen_and_setup": setup_s, "fold_720_steps_one_gpu": 720 * dt / args.steps},
@@ -837,7 +897,9 @@ def main():
                          "int_utilisation": (adds / (acc_ms * 1e-3) / 1e9 / MIXED_ADD_PEAK_GOPS) if acc_ms else 0.0,
                          "step_algorithmic_bytes": step_bytes, "step_hbm_frac": step_bytes / (dt / args.steps) / 1e9 / HBM_PEAK_GBPS},
         }
-        if not args.no_cpu_baseline and world == 1:      # the CPU baseline is timed at N = 1 only
+        if args.full:
+            out["verified"] = bool(ok)
+        if args.full and not args.no_cpu_baseline and world == 1:      # the CPU baseline is timed at N = 1 only
             cores = usable_cores()
             ck_host = params.ck.download(0, max(n_c, n_w))
             sps, secs, n_cpu, cph = cpu_baseline(circuit, mine, z_start, ck_host, args.cpu_seconds, cores)

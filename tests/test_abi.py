@@ -57,16 +57,39 @@ def test_no_cpu_fallback_without_gpu():
     assert e.value.code == _lib.ERR_NO_DEVICE
 
 
-def test_bench_sizes_its_cpu_baseline_by_the_usable_cores():
-    """bench.py's CPU baseline uses as many threads as the process may really run (affinity mask capped by the cgroup quota): at least
-    one, never more than the machine shows."""
+def _bench():
     import importlib.util
-    import os
     spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
     bench = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(bench)
-    n = bench.usable_cores()
+    return bench
+
+
+def test_bench_sizes_its_cpu_baseline_by_the_usable_cores():
+    """bench.py's CPU baseline uses as many threads as the process may really run (affinity mask capped by the cgroup quota): at least
+    one, never more than the machine shows."""
+    n = _bench().usable_cores()
     assert 1 <= n <= (os.cpu_count() or 1)
+
+
+def test_bench_dumps_outputs_as_exact_limbs_and_a_seeded_sample(tmp_path):
+    """bench.py --dump-outputs: every u64 word as two exact 32-bit limbs in float64; a vector longer than DUMP_SAMPLE elements cut to the
+    same seeded sample in every run, its indices beside it."""
+    import numpy as np
+    bench = _bench()
+    rng = np.random.default_rng(3)
+    long = rng.integers(0, np.iinfo(np.uint64).max, size=(bench.DUMP_SAMPLE + 5, 4), dtype=np.uint64, endpoint=True)
+    words = np.array([0, 1, (1 << 64) - 1], dtype=np.uint64)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"long": long, "words": words})
+    for name in ("long", "long_index", "words"):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+    idx = np.load(tmp_path / "a" / "long_index.npy").astype(np.int64)
+    limbs = np.load(tmp_path / "a" / "long.npy").astype(np.uint64).reshape(-1, 4, 2)
+    assert len(idx) == bench.DUMP_SAMPLE and np.array_equal(limbs[..., 0] | limbs[..., 1] << np.uint64(32), long[idx])
+    w = np.load(tmp_path / "a" / "words.npy").astype(np.uint64).reshape(-1, 2)
+    assert np.array_equal(w[:, 0] | w[:, 1] << np.uint64(32), words)
 
 
 def test_a_truncated_compressed_proof_is_an_invalid_argument():

@@ -26,7 +26,7 @@ for combo in itertools.product(*[v for _, v in axes]):
         if val != "-":
             env[k] = val
     for _ in range(reps):
-        r = subprocess.run([sys.executable, root + "/bench.py"] + extra.split(), env=env, capture_output=True, text=True, timeout=600)
+        r = subprocess.run([sys.executable, root + "/bench.py", "--full"] + extra.split(), env=env, capture_output=True, text=True, timeout=600)
         try:
             d = json.loads(r.stdout.strip().splitlines()[-1])
         except Exception:

@@ -21,4 +21,4 @@ for rep in 1 2; do timeout 600 python3 tools/e2e.py contrast HD 1 cyclefold 2>/d
 echo "== whole images"
 for cfg in "contrast HD 3 ivc" "contrast HD 3 ivc" "contrast HD 1 ivc" "crop HD 3 ivc" "contrast HD 2 accumulator" "contrast HD 3 cyclefold"; do timeout 600 python3 tools/e2e.py $cfg 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('whole image', d['config'], d['mode'], d['segments'], d['steps'], round(d['steps_per_s'],1), d['verified'], d['final_state'][0][:18])"; done
 echo "== bench, three times"
-for rep in 1 2 3; do timeout 600 python3 bench.py --no-extras --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('bench', round(d['value'],1), d['verified'], 'compressed', d['compressed_snark']['verified'] if d.get('compressed_snark') else None)"; done
+for rep in 1 2 3; do timeout 600 python3 bench.py --full --no-extras --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('bench', round(d['value'],1), d['verified'], 'compressed', d['compressed_snark']['verified'] if d.get('compressed_snark') else None)"; done

@@ -32,7 +32,7 @@ def main():
         # the per-step MSM(T) launches: the launch class that moves the most bytes in all (the few larger launches are the merges')
         k = max(acc, key=lambda x: acc[x]["launches"] * acc[x]["hbm_bytes_per_launch"])
         out[key] = {"kernel": k, "hbm_bytes_per_launch": acc[k]["hbm_bytes_per_launch"], "launches": acc[k]["launches"],
-                    "method": f"rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes of `bench.py --no-cpu-baseline --no-extras --no-compress {cmd}` "
+                    "method": f"rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes of `bench.py --full --no-cpu-baseline --no-extras --no-compress {cmd}` "
                               f"(tools/refresh_profiles.sh, round {tag}); bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024 (gfx950 FETCH_SIZE halving, MI355X_MICROARCH.md §HBM); "
                               "these are L2 misses, most of them served by the 256 MB Infinity Cache",
                     "source": f"profiles/{tag}_pmc_summary_{mode}.json (separate PMC passes of the same command; not measured inside this run)",
