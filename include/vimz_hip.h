@@ -113,6 +113,26 @@ void vimz_bases_free(vimz_ctx* ctx, vimz_bases* b);
 size_t vimz_pack_count(size_t height, size_t width, int block);
 int vimz_pack_pixels(vimz_ctx* ctx, const uint8_t* pixels, size_t height, size_t width, int channels, int block, uint64_t* out);
 
+/* ---- image hashes: the running Poseidon hash the circuits keep of an image (circuits/src/utils/hashers.circom,
+ *      image_running_hash.circom; what pyvimz's image-hasher writes to marketplace/image-data/ .hash files and what a proof's final
+ *      state holds in z_n[0] / z_n[1]).  Per unit (a row, or a block x block square) d = ArrayHasher(L)(unit elements); then
+ *      acc_0 = 0, acc_{i+1} = PairHasher(acc_i, d_i), or PairHasher(acc_i, 0) for a unit whose `drop` flag is set (redact's target).
+ *      Units are packed as vimz_pack_pixels packs them.  The unit digests of all n images go to the GPU in one launch; the serial
+ *      chain over them runs on the host, one image per thread.  out: n hashes, canonical (4 x u64 each). ---------------------- */
+typedef struct {
+  const uint8_t* pixels;      /* height x width x channels bytes; channels 1 (grey, in the R slot), 3 (RGB) or 4 (RGBA, alpha ignored) ... */
+  size_t height, width;
+  int channels;
+  const uint64_t* units;      /* ... or, pixels == NULL: n_units x unit_len pre-packed canonical elements (each below the modulus) */
+  size_t n_units, unit_len;
+  int block;                  /* 0: row-wise; 40: 40 x 40 blocks as vimz_pack_pixels(block = 40) (redact).  0 for pre-packed units */
+  size_t max_units;           /* 0: every unit; else only the first max_units rows / blocks (at most as many as the image has) */
+  const uint8_t* drop;        /* optional, one flag per hashed unit: nonzero -> that unit's digest is replaced by 0 */
+} vimz_image_desc;
+int vimz_image_hash(vimz_ctx* ctx, const vimz_image_desc* imgs, size_t n, uint64_t* out);
+/* wall-clock milliseconds of the context's last vimz_image_hash: ms[0] the digests (uploads, kernel, download), ms[1] the host chains */
+int vimz_image_hash_last_profile(vimz_ctx* ctx, double ms[2]);
+
 /* ---- device vectors -------------------------------------------------------------------------------- */
 int vimz_vec_alloc(vimz_ctx* ctx, int field, size_t n, vimz_vec** out); /* zero-filled */
 int vimz_vec_upload(vimz_ctx* ctx, vimz_vec* v, size_t offset, const uint64_t* host, size_t n, int form);

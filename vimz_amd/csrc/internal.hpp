@@ -28,6 +28,13 @@ struct vimz_ctx {
   // the streams, prover_internal.hpp: wait_row_flag — but kept: no stream creation per fold call.)
   std::mutex stream_mu;
   std::vector<std::pair<int, hipStream_t>> spare_streams;     // (priority, stream)
+  uint32_t* image_hash_tables = nullptr;      // Poseidon constants t = 2..9 for vimz_image_hash (image_hash.hip), uploaded on first use
+  // vimz_image_hash's device buffer: grows, never shrinks; a buffer it outgrew is kept until the context goes (a hipFree would wait for the
+  // whole device — for the folds of other contexts on it)
+  void* image_hash_buf = nullptr;
+  size_t image_hash_bytes = 0;
+  std::vector<void*> image_hash_retired;
+  double image_hash_ms[2] = {};               // the last vimz_image_hash: digests (uploads, kernel, download), host chains
 };
 // a non-blocking stream of the given priority on c's device (caller has set the device): a recycled one if there is one
 static inline hipError_t vz_stream_acquire(vimz_ctx* c, int priority, hipStream_t* out) {

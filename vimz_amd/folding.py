@@ -359,3 +359,99 @@ def verify_compressed_proof(verifier_key, compressed, num_steps, initial_state):
         r = verifier_key.verify_compressed(compressed, num_steps, initial_state)
     if r != 0:
         raise _lib.VimzError(_lib.ERR_UNSAT, f"Failed to verify proof (flags {r:#x})")
+
+
+# ---- a proof's final state against its images (the Sonobe path's verify_final_state_arkworks, vimz/src/sonobe_backend/folding.rs:77-132) ----
+
+def _gpu_hasher(ctx):
+    from . import image_hasher
+
+    def run(specs):
+        return image_hasher.image_hashes(ctx, specs)
+    return run
+
+
+def _hash_specs(hasher, specs, ctx=None):
+    """hasher: a callable specs -> [int] (tests inject the CPU oracle), a hip.Context, or None (the GPU: `ctx` if given, else a context on device 0
+    for this call).  Every spec goes in ONE call: the source and the target of a proof are hashed together."""
+    if callable(hasher) and not hasattr(hasher, "image_hash"):
+        return hasher(specs)
+    if hasher is not None:
+        return _gpu_hasher(hasher)(specs)
+    if ctx is not None:
+        return _gpu_hasher(ctx)(specs)
+    from .hip import Context
+    with Context(0) as c:
+        return _gpu_hasher(c)(specs)
+
+
+def final_state_units(transformation, resolution="HD", demo=False):
+    """(steps n, source units, target units) of a proof of `transformation`: n is its step count (DEMO_STEPS at most in demo mode), and it hashes
+    n rows (blocks for redact) of each image into its final state — resize a·n source rows and b·n target rows (RATIO_TO_LOWER)."""
+    n = iteration_count(transformation, resolution)
+    if demo:
+        n = min(n, DEMO_STEPS)
+    if transformation == "resize":
+        a, b = RATIO_TO_LOWER[resolution]
+        return n, a * n, b * n
+    return n, n, n
+
+
+def expected_final_state(transformation, source, target, resolution="HD", demo=False, redact=None, hasher=None, ctx=None):
+    """{index: value}: the entries of a proof's final state z_n that the images determine — z_n[0] the running hash of `source`, z_n[1] that of
+    `target` (either may be None: not checked).  Images are arrays or paths (vimz_amd.image_hasher).
+        hash              z[0] only: the transformation has no target
+        blur / sharpness  z[0] is the hash of the UNPADDED source (the circuit hashes the middle of its three rows); z[2], z[3] are row bookkeeping
+        resize            a·n source rows, b·n target rows, each image at its own width
+        redact            40 x 40 blocks; the target's redacted blocks enter as PairHasher(acc, 0), not as the digest of a black block, so the
+                          target needs `redact` (the input's flags)
+        crop              the target is refused: the crop circuit's z[1] is not the hash of the cropped image (its decoder reads the offsets from
+                          other bit fields than the input's `info` encodes and packs the R byte alone, SURVEY.md F6 — tests/test_image_hash_host.py
+                          shows it on the oracle)
+    hasher: None (the GPU, on `ctx` or a context of its own), a hip.Context, or a callable taking the request dicts of image_hasher.image_hashes."""
+    if transformation not in ("blur", "brightness", "contrast", "crop", "grayscale", "hash", "redact", "resize", "sharpness"):
+        raise ValueError(transformation)
+    n, n_src, n_tgt = final_state_units(transformation, resolution, demo)
+    mode = "blocks" if transformation == "redact" else "rows"
+    specs, idx = [], []
+    if source is not None:
+        specs.append({"image": source, "mode": mode, "units": n_src})
+        idx.append(0)
+    if target is not None:
+        if transformation == "hash":
+            raise _lib.VimzError(_lib.ERR_INVALID, "A proof of `hash` determines no target image")
+        if transformation == "crop":
+            raise _lib.VimzError(_lib.ERR_INVALID, "Target image check is not supported for crop: the crop circuit's final state is not the hash of "
+                                                    "the cropped image (SURVEY.md F6)")
+        spec = {"image": target, "mode": mode, "units": n_tgt}
+        if transformation == "redact":
+            if redact is None:
+                raise _lib.VimzError(_lib.ERR_INVALID, "redact: the target image's hash needs the input's redact flags (redact=)")
+            flags = [int(v) for v in list(redact)[:n_tgt]]
+            if len(flags) < n_tgt:
+                raise _lib.VimzError(_lib.ERR_INVALID, f"redact: {len(flags)} redact flags for {n_tgt} blocks")
+            spec["drop"] = flags
+        specs.append(spec)
+        idx.append(1)
+    if not specs:
+        return {}
+    return dict(zip(idx, [int(v) for v in _hash_specs(hasher, specs, ctx)]))
+
+
+def verify_final_state(proof_or_state, transformation, source_image=None, target_image=None, resolution="HD", demo=False, redact=None, hasher=None):
+    """verify_final_state_arkworks (vimz/src/sonobe_backend/folding.rs:77-132): the final state of a proof against the images it claims to be about.
+    proof_or_state: a FoldingProof of any mode (its step count must be the transformation's, as the reference asserts) or a plain z_n (e.g. the
+    decider's public z_i).  Raises VimzError(ERR_UNSAT, "Source image hash does not match final state") or the Target equivalent."""
+    ctx = None
+    if isinstance(proof_or_state, FoldingProof):
+        n = final_state_units(transformation, resolution, demo)[0]
+        if proof_or_state.steps != n:
+            raise _lib.VimzError(_lib.ERR_UNSAT, f"The proof folds {proof_or_state.steps} steps, {transformation} at {resolution} takes {n}")
+        z = [int(v) for v in proof_or_state.state()]
+        ctx = getattr(proof_or_state.prover, "ctx", None)
+    else:
+        z = [int(v) for v in proof_or_state]
+    exp = expected_final_state(transformation, source_image, target_image, resolution, demo, redact, hasher, ctx)
+    for i, who in ((0, "Source"), (1, "Target")):
+        if i in exp and (i >= len(z) or z[i] != exp[i]):
+            raise _lib.VimzError(_lib.ERR_UNSAT, f"{who} image hash does not match final state")

@@ -58,6 +58,13 @@ class Bases:
             self.h = None
 
 
+class ImageDesc(C.Structure):
+    """vimz_image_desc (include/vimz_hip.h)."""
+    _fields_ = [("pixels", C.c_void_p), ("height", C.c_size_t), ("width", C.c_size_t), ("channels", C.c_int),
+                ("units", C.c_void_p), ("n_units", C.c_size_t), ("unit_len", C.c_size_t), ("block", C.c_int),
+                ("max_units", C.c_size_t), ("drop", C.c_void_p)]
+
+
 class Context:
     """One per GPU (vimz_ctx)."""
 
@@ -184,6 +191,44 @@ class Context:
             per = block * ((block + 9) // 10)
             return out.reshape(-1, per, 4)
         return out.reshape(h, -1, 4)
+
+    def image_hash(self, descs):
+        """vimz_image_hash over n images in one call.  descs: dicts with either `pixels` ((H, W) or (H, W, C) uint8, C = 1, 3 or 4) or `units`
+        ((U, L, 4) uint64 canonical elements), and optionally `block` (0 / 40), `max_units`, `drop` (uint8 flags, one per hashed unit).
+        Returns the n running hashes as ints.  (The arrays' lengths are the caller's to check: vimz_amd.image_hasher does.)"""
+        n = len(descs)
+        arr = (ImageDesc * n)()
+        keep = []
+        for i, d in enumerate(descs):
+            D = arr[i]
+            if d.get("pixels") is not None:
+                px = np.ascontiguousarray(d["pixels"], dtype=np.uint8)
+                keep.append(px)
+                D.pixels = px.ctypes.data
+                D.height, D.width = px.shape[0], px.shape[1]
+                D.channels = 1 if px.ndim == 2 else px.shape[2]
+            else:
+                u = _u64(d["units"])
+                keep.append(u)
+                D.units = u.ctypes.data
+                D.n_units, D.unit_len = u.shape[0], u.shape[1]
+            D.block = int(d.get("block", 0))
+            D.max_units = int(d.get("max_units", 0) or 0)
+            if d.get("drop") is not None:
+                dr = np.ascontiguousarray(d["drop"], dtype=np.uint8)
+                keep.append(dr)
+                D.drop = dr.ctypes.data
+        out = np.zeros((n, 4), dtype=np.uint64)
+        self.lib.vimz_image_hash.argtypes = [C.c_void_p, C.POINTER(ImageDesc), C.c_size_t, C.c_void_p]
+        self._chk(self.lib.vimz_image_hash(self.h, arr, n, _ptr(out)))
+        return [sum(int(r[k]) << (64 * k) for k in range(4)) for r in out]
+
+    def image_hash_last_profile(self):
+        """Milliseconds of the last image_hash call: {"digests": uploads + kernel + download, "chain": the host chains}."""
+        ms = (C.c_double * 2)()
+        self.lib.vimz_image_hash_last_profile.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        self._chk(self.lib.vimz_image_hash_last_profile(self.h, ms))
+        return {"digests": ms[0], "chain": ms[1]}
 
     # ---- MSM
     def msm(self, bases, scalars, form=L.FORM_CANONICAL, window_bits=0, out_form=L.FORM_CANONICAL):
