@@ -133,6 +133,55 @@ int vimz_image_hash(vimz_ctx* ctx, const vimz_image_desc* imgs, size_t n, uint64
 /* wall-clock milliseconds of the context's last vimz_image_hash: ms[0] the digests (uploads, kernel, download), ms[1] the host chains */
 int vimz_image_hash_last_profile(vimz_ctx* ctx, double ms[2]);
 
+/* ---- image edits: pyvimz's image-editor transformations (pyvimz/pyvimz/img/transformations.py, restated bit-exactly by
+ *      vimz_amd/image_editor.py) on the device, with the packing of the prover's input fused in.  One call runs n edit descriptors in
+ *      order on the context's stream; a descriptor's source is host pixels or the edited image of an earlier descriptor of the same call
+ *      (which stays on the device).  Outputs, each optional:
+ *        out_pixels  the edited image, height x width x channels bytes as vimz_image_edit_shapes reports them
+ *        out_source  the source packed as vimz_amd.image_editor.build_input's "original": rows of ceil(width/10) elements; blur and
+ *                    sharpness add one zero row above and one below; redact packs 40 x 40 blocks (height and width multiples of 40)
+ *        out_target  the edited image packed as build_input's "transformed" (rows, or blocks for redact; none for VIMZ_EDIT_HASH)
+ *      Packed elements are canonical, 4 x u64 each.  Sources of 4 channels have their alpha ignored; an RGB edit of them has 3 channels.
+ *      Grey sources (1 channel) are accepted by hash, crop and redact only. ---------------------------------------------------- */
+#define VIMZ_EDIT_HASH 0        /* no edit: the source's packing (and a copy of its pixels) */
+#define VIMZ_EDIT_GRAYSCALE 1   /* (19595 R + 38470 G + 7471 B + 32768) >> 16, one channel */
+#define VIMZ_EDIT_BRIGHTNESS 2  /* clip(c * factor, 0, 255) truncated, in float64 */
+#define VIMZ_EDIT_CONTRAST 3    /* clip((c - 128.0) * factor + 128.0, 0, 255) truncated, in float64 */
+#define VIMZ_EDIT_BLUR 4        /* 3 x 3 box, zero padding, sum / 9 */
+#define VIMZ_EDIT_SHARPNESS 5   /* 5c - up - down - left - right, zero padding, clamped */
+#define VIMZ_EDIT_RESIZE 6      /* to new_width x new_height: image_editor.resize_image's float64 interpolation */
+#define VIMZ_EDIT_CROP 7        /* the new_width x new_height window at (x, y), inside the image */
+#define VIMZ_EDIT_REDACT 8      /* zero the flagged full 40 x 40 blocks */
+typedef struct {
+  int op;                     /* VIMZ_EDIT_* */
+  const uint8_t* pixels;      /* the source: height x width x channels bytes (channels 1, 3 or 4) ... */
+  size_t height, width;
+  int channels;
+  int64_t source;             /* ... or, pixels == NULL: the index of an earlier descriptor of the call, whose edited image is the source */
+  double factor;              /* brightness, contrast (finite) */
+  size_t x, y;                /* crop: the window's top-left corner */
+  size_t new_width, new_height;     /* crop: the window's size; resize: the target size */
+  const uint8_t* redact;      /* redact: NULL (with n_redact = 0) for pyvimz's checkerboard (block (by, bx) when by + bx is odd), or one flag per
+                                 full block, row-major (non-NULL even when there are no full blocks) */
+  size_t n_redact;            /* the number of flags: (height / 40) * (width / 40); any other count is refused, 0 included */
+  uint8_t* out_pixels;        /* optional outputs (NULL: not wanted), sized by vimz_image_edit_shapes */
+  uint64_t* out_source;
+  uint64_t* out_target;
+} vimz_edit_desc;
+typedef struct {
+  size_t height, width;       /* the edited image */
+  int channels;               /* 1 or 3 */
+  size_t source_units, source_unit_len;     /* out_source: source_units x source_unit_len elements (rows, or 40 x 40 blocks of 160) */
+  size_t target_units, target_unit_len;     /* out_target (0 x 0 for hash) */
+} vimz_edit_shape;
+/* n: 1 to 4096 descriptors per call (VIMZ_ERR_INVALID otherwise) */
+#define VIMZ_EDIT_MAX_DESCS 4096
+/* checks the n descriptors as vimz_image_edit does (their outputs may be NULL) and writes each one's shapes to out[i] */
+int vimz_image_edit_shapes(vimz_ctx* ctx, const vimz_edit_desc* descs, size_t n, vimz_edit_shape* out);
+int vimz_image_edit(vimz_ctx* ctx, const vimz_edit_desc* descs, size_t n);
+/* wall-clock milliseconds of the context's last vimz_image_edit: ms[0] uploads, ms[1] the kernels, ms[2] downloads */
+int vimz_image_edit_last_profile(vimz_ctx* ctx, double ms[3]);
+
 /* ---- device vectors -------------------------------------------------------------------------------- */
 int vimz_vec_alloc(vimz_ctx* ctx, int field, size_t n, vimz_vec** out); /* zero-filled */
 int vimz_vec_upload(vimz_ctx* ctx, vimz_vec* v, size_t offset, const uint64_t* host, size_t n, int form);

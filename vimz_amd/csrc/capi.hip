@@ -229,6 +229,8 @@ void vimz_ctx_destroy(vimz_ctx* c) {
   if (c->image_hash_tables) hipFree(c->image_hash_tables);
   if (c->image_hash_buf) hipFree(c->image_hash_buf);
   for (void* p : c->image_hash_retired) hipFree(p);
+  if (c->image_edit_buf) hipFree(c->image_edit_buf);
+  for (void* p : c->image_edit_retired) hipFree(p);
   for (int i = 0; i < 7; i++) if (c->ev[i]) hipEventDestroy(c->ev[i]);
   hipEventDestroy(c->t0); hipEventDestroy(c->t1);
   for (auto& ps : c->spare_streams) hipStreamDestroy(ps.second);

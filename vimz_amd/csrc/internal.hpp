@@ -35,6 +35,11 @@ struct vimz_ctx {
   size_t image_hash_bytes = 0;
   std::vector<void*> image_hash_retired;
   double image_hash_ms[2] = {};               // the last vimz_image_hash: digests (uploads, kernel, download), host chains
+  // vimz_image_edit's device buffer (image_edit.hip): grow-only as image_hash_buf, for the same reason
+  void* image_edit_buf = nullptr;
+  size_t image_edit_bytes = 0;
+  std::vector<void*> image_edit_retired;
+  double image_edit_ms[3] = {};               // the last vimz_image_edit: uploads, kernels, downloads
 };
 // a non-blocking stream of the given priority on c's device (caller has set the device): a recycled one if there is one
 static inline hipError_t vz_stream_acquire(vimz_ctx* c, int priority, hipStream_t* out) {

@@ -65,6 +65,25 @@ class ImageDesc(C.Structure):
                 ("max_units", C.c_size_t), ("drop", C.c_void_p)]
 
 
+_NO_FLAGS = np.zeros(1, dtype=np.uint8)       # a non-NULL address for an empty redact flag list
+
+EDIT_OPS = {"hash": 0, "grayscale": 1, "brightness": 2, "contrast": 3, "blur": 4, "sharpness": 5, "resize": 6, "crop": 7, "redact": 8}
+
+
+class EditDesc(C.Structure):
+    """vimz_edit_desc (include/vimz_hip.h)."""
+    _fields_ = [("op", C.c_int), ("pixels", C.c_void_p), ("height", C.c_size_t), ("width", C.c_size_t), ("channels", C.c_int),
+                ("source", C.c_int64), ("factor", C.c_double), ("x", C.c_size_t), ("y", C.c_size_t), ("new_width", C.c_size_t),
+                ("new_height", C.c_size_t), ("redact", C.c_void_p), ("n_redact", C.c_size_t), ("out_pixels", C.c_void_p),
+                ("out_source", C.c_void_p), ("out_target", C.c_void_p)]
+
+
+class EditShape(C.Structure):
+    """vimz_edit_shape (include/vimz_hip.h)."""
+    _fields_ = [("height", C.c_size_t), ("width", C.c_size_t), ("channels", C.c_int), ("source_units", C.c_size_t), ("source_unit_len", C.c_size_t),
+                ("target_units", C.c_size_t), ("target_unit_len", C.c_size_t)]
+
+
 class Context:
     """One per GPU (vimz_ctx)."""
 
@@ -229,6 +248,71 @@ class Context:
         self.lib.vimz_image_hash_last_profile.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         self._chk(self.lib.vimz_image_hash_last_profile(self.h, ms))
         return {"digests": ms[0], "chain": ms[1]}
+
+    def image_edit(self, descs):
+        """vimz_image_edit over n edit descriptors in one call, in order.  descs: dicts with
+            op        a name of EDIT_OPS (or its number)
+            pixels    the source, (H, W) or (H, W, C) uint8 with C = 1, 3 or 4 ... or
+            source    the index of an earlier descriptor of the call, whose edited image (kept on the device) is the source
+            factor, x, y, new_width, new_height, redact (uint8 flags, one per full 40 x 40 block)   the op's parameters
+            want      the outputs to bring back, a subset of ("pixels", "source", "target") (default: all the op has)
+        Returns one dict per descriptor {"pixels": (H', W'[, 3]) uint8, "source": (units, len, 4) uint64, "target": ...}, None where not wanted.
+        (Arguments are checked by the library: a bad one raises VimzError(ERR_INVALID).)"""
+        n = len(descs)
+        arr = (EditDesc * n)()
+        keep = []
+        for i, d in enumerate(descs):
+            D = arr[i]
+            op = d.get("op")
+            D.op = EDIT_OPS.get(op, -1) if isinstance(op, str) else int(op)
+            if d.get("pixels") is not None:
+                px = np.ascontiguousarray(d["pixels"], dtype=np.uint8)
+                if px.ndim == 3 and px.shape[2] == 1:
+                    px = px[:, :, 0]
+                keep.append(px)
+                D.pixels = px.ctypes.data
+                D.height, D.width = px.shape[0], px.shape[1]
+                D.channels = 1 if px.ndim == 2 else px.shape[2]
+            else:
+                D.source = int(d.get("source", -1))
+            D.factor = float(d.get("factor") or 0.0)
+            D.x, D.y = int(d.get("x") or 0), int(d.get("y") or 0)
+            D.new_width, D.new_height = int(d.get("new_width") or 0), int(d.get("new_height") or 0)
+            if d.get("redact") is not None:
+                fl = np.ascontiguousarray(np.asarray(d["redact"]).reshape(-1) != 0, dtype=np.uint8)
+                keep.append(fl)
+                D.redact = fl.ctypes.data if fl.size else _NO_FLAGS.ctypes.data     # (never NULL: NULL asks for the checkerboard)
+                D.n_redact = fl.size
+        lib = self.lib
+        lib.vimz_image_edit_shapes.argtypes = [C.c_void_p, C.POINTER(EditDesc), C.c_size_t, C.POINTER(EditShape)]
+        lib.vimz_image_edit.argtypes = [C.c_void_p, C.POINTER(EditDesc), C.c_size_t]
+        shapes = (EditShape * max(n, 1))()
+        self._chk(lib.vimz_image_edit_shapes(self.h, arr, n, shapes))
+        out = []
+        dummy = np.zeros(4, dtype=np.uint64)       # (a packed output the op cannot give, e.g. redact's blocks of a 41 x 37 image: the library refuses it)
+        for i, d in enumerate(descs):
+            S, D = shapes[i], arr[i]
+            want = d.get("want", ("pixels", "source", "target"))
+            r = {"pixels": None, "source": None, "target": None}
+            if "pixels" in want:
+                r["pixels"] = np.empty((S.height, S.width) if S.channels == 1 else (S.height, S.width, S.channels), dtype=np.uint8)
+                D.out_pixels = r["pixels"].ctypes.data
+            if "source" in want:
+                r["source"] = np.empty((S.source_units, S.source_unit_len, 4), dtype=np.uint64)
+                D.out_source = r["source"].ctypes.data if r["source"].size else dummy.ctypes.data
+            if "target" in want and D.op != EDIT_OPS["hash"]:
+                r["target"] = np.empty((S.target_units, S.target_unit_len, 4), dtype=np.uint64)
+                D.out_target = r["target"].ctypes.data if r["target"].size else dummy.ctypes.data
+            out.append(r)
+        self._chk(lib.vimz_image_edit(self.h, arr, n))
+        return out
+
+    def image_edit_last_profile(self):
+        """Milliseconds of the last image_edit call: {"upload", "kernels", "download"}."""
+        ms = (C.c_double * 3)()
+        self.lib.vimz_image_edit_last_profile.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        self._chk(self.lib.vimz_image_edit_last_profile(self.h, ms))
+        return {"upload": ms[0], "kernels": ms[1], "download": ms[2]}
 
     # ---- MSM
     def msm(self, bases, scalars, form=L.FORM_CANONICAL, window_bits=0, out_form=L.FORM_CANONICAL):

@@ -11,8 +11,17 @@ in bits [24k, 24k+24), R in the low byte — i.e. the 30 little-endian bytes of 
 the raw R,G,B bytes of its 10 pixels.  Grayscale: the value sits in the low byte of each 24-bit slot.
 Rows are returned as uint64 limb arrays of shape (rows, width, 4) (canonical little-endian), the
 layout the C ABI (include/vimz_hip.h) takes; `rows_to_hex` renders the reference's "0x…" strings.
+
+The functions below are the specification.  gpu_edit, gpu_build_input and gpu_edit_chain compute the same bytes on the GPU
+(vimz_image_edit, vimz_amd/csrc/image_edit.hip); they have no CPU path.  The command line is the GPU editor, as pyvimz's `image-editor`:
+
+    python -m vimz_amd.image_editor OPERATION -i IMAGE [-o OUT] [--save-png PNG] [--factor F] [--x X --y Y --crop-size SD|HD|FHD]
+                                    [--resize-option "HD to SD"|"4K to FHD"] [--redact-flags FILE] [--device D]
 """
+import argparse
 import json
+import os
+import sys
 
 import numpy as np
 
@@ -221,3 +230,200 @@ def load_json(path):
     if "redact" in d:
         out["redact"] = [int(s, 16) for s in d["redact"]]
     return out
+
+
+# ---------------------------------------------------------------- the same edits on the GPU (vimz_image_edit)
+
+OPERATIONS = ("blur", "brightness", "contrast", "crop", "grayscale", "hash", "redact", "resize", "sharpness")
+RESIZE_OPTIONS = {"hd to sd": (640, 480), "4k to fhd": (1920, 1080)}      # pyvimz image_editor.py's --resize-option
+BLOCK = 40
+
+
+def _crop_wh(crop_size):
+    if isinstance(crop_size, str):
+        if crop_size.lower() not in SIZE_MAP:
+            raise ValueError(f"crop size {crop_size!r}: one of SD, HD, FHD, or a (width, height) pair")
+        return SIZE_MAP[crop_size.lower()]
+    w, h = crop_size
+    return int(w), int(h)
+
+
+def _edit_desc(op, factor=None, x=None, y=None, crop_size=None, resize_to=None, redact=None):
+    """The parameters of `op` as a hip.Context.image_edit descriptor (without its source)."""
+    if op not in OPERATIONS:
+        raise ValueError(f"unknown operation {op!r}")
+    d = {"op": op}
+    if op in ("brightness", "contrast"):
+        if factor is None:
+            raise ValueError(f"{op} needs a factor")
+        d["factor"] = float(factor)
+    elif op == "crop":
+        if x is None or y is None or crop_size is None:
+            raise ValueError("crop needs x, y and crop_size")
+        w, h = _crop_wh(crop_size)
+        d.update(x=int(x), y=int(y), new_width=w, new_height=h)
+    elif op == "resize":
+        if resize_to is None:
+            raise ValueError("resize needs resize_to = (width, height)")
+        w, h = resize_to
+        d.update(new_width=int(w), new_height=int(h))
+    elif op == "redact" and redact is not None:
+        d["redact"] = np.asarray(redact).reshape(-1)
+    return d
+
+
+def _input_fields(op, params, shape):
+    """build_input's scalar fields of `op` for a source of `shape`: factor, info, or the redact flags (pyvimz's checkerboard by default)."""
+    out = {}
+    if op in ("brightness", "contrast"):
+        out["factor"] = int(params["factor"] * 10)
+    elif op == "crop":
+        out["info"] = params["x"] * 2 ** 24 + params["y"] * 2 ** 12
+    elif op == "redact":
+        if params.get("redact") is not None:
+            out["redact"] = [1 if v else 0 for v in np.asarray(params["redact"]).reshape(-1)]
+        else:
+            out["redact"] = [(by + bx) % 2 for by in range(shape[0] // BLOCK) for bx in range(shape[1] // BLOCK)]
+    return out
+
+
+def _source(image):
+    img = np.asarray(image)
+    if img.dtype != np.uint8:
+        raise ValueError(f"an image is uint8, not {img.dtype}")
+    return img
+
+
+def _run(ctx, descs):
+    if ctx is not None:
+        return ctx.image_edit(descs)
+    from .hip import Context
+    with Context(0) as c:
+        return c.image_edit(descs)
+
+
+def _as_input(op, params, shape, res):
+    inp = {"original": res["source"], "transformed": res["target"]}
+    inp.update(_input_fields(op, params, shape))
+    return inp
+
+
+def gpu_edit(ctx, op, image, **params):
+    """The edited image of `op` on the GPU: the bytes the host function above returns for image[..., :3] (redact: its image, not its flags).
+    params: factor (brightness, contrast), x, y, crop_size ("SD" / "HD" / "FHD" or (width, height)), resize_to ((width, height)), redact (one
+    flag per full 40 x 40 block, row-major; default pyvimz's checkerboard).  ctx: a hip.Context, or None for a context on device 0."""
+    d = _edit_desc(op, **params)
+    d.update(pixels=_source(image), want=("pixels",))
+    return _run(ctx, [d])[0]["pixels"]
+
+
+def gpu_build_input(ctx, op, image, factor=None, x=None, y=None, crop_size=None, resize_to=None, redact=None):
+    """build_input on the GPU: the same arrays and fields.  redact= takes the caller's flags (one per full 40 x 40 block, row-major), which
+    build_input cannot; the input's "redact" field then holds them."""
+    params = {"factor": factor, "x": x, "y": y, "crop_size": crop_size, "resize_to": resize_to, "redact": redact}
+    img = _source(image)
+    d = _edit_desc(op, **params)
+    d.update(pixels=img, want=("source", "target"))
+    return _as_input(op, params, img.shape, _run(ctx, [d])[0])
+
+
+def gpu_edit_chain(ctx, image, stages):
+    """Several edits in ONE call, each on the previous one's result (kept on the device): stages = [(op, params), ...], e.g.
+    [("sharpness", {}), ("grayscale", {})].  Returns one (edited image, build_input dict of that stage) per stage."""
+    img = _source(image)
+    descs = []
+    for i, (op, params) in enumerate(stages):
+        d = _edit_desc(op, **dict(params))
+        if i == 0:
+            d["pixels"] = img
+        else:
+            d["source"] = i - 1
+        descs.append(d)
+    if not descs:
+        return []
+    res = _run(ctx, descs)
+    out, shape = [], img.shape
+    for (op, params), r in zip(stages, res):
+        p = {"factor": None, "x": None, "y": None, "redact": None}
+        p.update(params)
+        out.append((r["pixels"], _as_input(op, p, shape, r)))
+        shape = r["pixels"].shape
+    return out
+
+
+def _load(path):
+    from PIL import Image
+    with Image.open(path) as im:
+        if im.mode not in ("L", "RGB", "RGBA"):
+            im = im.convert("RGB")
+        return np.array(im)
+
+
+def _read_flags(path):
+    """--redact-flags: a JSON list of 0 / 1 (or the input JSON's "0x0" / "0x1" strings), or whitespace-separated 0 / 1."""
+    with open(path) as fp:
+        text = fp.read()
+    try:
+        vals = json.loads(text)
+    except ValueError:
+        vals = text.split()
+    if isinstance(vals, dict):
+        vals = vals.get("redact")
+    if not isinstance(vals, list):
+        raise ValueError(f"{path}: not a list of flags")
+    return [int(v, 0) if isinstance(v, str) else int(v) for v in vals]
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m vimz_amd.image_editor",
+                                 description="Edit an image on the GPU and write the prover's input JSON (pyvimz's image-editor).")
+    ap.add_argument("operation", choices=OPERATIONS)
+    ap.add_argument("--image-path", "-i", required=True, help="the source image")
+    ap.add_argument("--output", "-o", default="./", help="a file, or a directory for <operation>.json (default: the current directory)")
+    ap.add_argument("--save-png", help="also save the edited image as a PNG")
+    ap.add_argument("--factor", type=float, help="brightness, contrast")
+    ap.add_argument("--x", type=int, help="crop: the window's left column")
+    ap.add_argument("--y", type=int, help="crop: the window's top row")
+    ap.add_argument("--crop-size", choices=["SD", "HD", "FHD"])
+    ap.add_argument("--resize-option", choices=["HD to SD", "4K to FHD"])
+    ap.add_argument("--redact-flags", help="redact: a file of flags, one per full 40 x 40 block, row-major (default: pyvimz's checkerboard)")
+    ap.add_argument("--device", type=int, default=0)
+    a = ap.parse_args(argv)
+    op = a.operation
+    if op in ("brightness", "contrast") and a.factor is None:
+        ap.error(f"{op} needs --factor")
+    if op == "crop" and (a.x is None or a.y is None or a.crop_size is None):
+        ap.error("crop needs --x, --y and --crop-size")
+    if op == "resize" and a.resize_option is None:
+        ap.error("resize needs --resize-option")
+    if a.redact_flags is not None and op != "redact":
+        ap.error("--redact-flags is for redact only")
+    try:
+        flags = _read_flags(a.redact_flags) if a.redact_flags else None
+        img = _load(a.image_path)
+    except (OSError, ValueError) as e:
+        print(f"image_editor: {e}", file=sys.stderr)
+        return 1
+    params = {"factor": a.factor, "x": a.x, "y": a.y, "crop_size": a.crop_size, "redact": flags,
+              "resize_to": RESIZE_OPTIONS[a.resize_option.lower()] if a.resize_option else None}
+    from . import _lib, hip
+    try:
+        with hip.Context(a.device) as ctx:
+            d = _edit_desc(op, **params)
+            d["pixels"] = img
+            res = ctx.image_edit([d])[0]
+    except (_lib.VimzError, ValueError) as e:
+        print(f"image_editor: {e}", file=sys.stderr)
+        return 1
+    out = os.path.join(a.output, f"{op}.json") if os.path.isdir(a.output) else a.output
+    dump_json(_as_input(op, params, img.shape, res), out)
+    print(f"Transformation {op} applied successfully. Data saved to {out}.")
+    if a.save_png and op != "hash":
+        from PIL import Image
+        Image.fromarray(res["pixels"]).save(a.save_png)
+        print(f"Transformed image saved as {a.save_png}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
