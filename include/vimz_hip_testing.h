@@ -49,6 +49,21 @@ int vimz_decider_selfcheck(int steps, int full, uint32_t* result, uint64_t count
 int vimz_testing_kzg_setup_seeded(vimz_ctx* ctx, const uint8_t* seed, size_t seed_len, size_t n, vimz_bases** srs_out, uint64_t vk_g2_out[16]);
 int vimz_testing_decider_setup_seeded(vimz_cf* prover, const uint64_t kzg_vk_g2[16], int light, const uint8_t* seed, size_t seed_len, vimz_decider** out, double seconds[4]);
 
+/* ONE operation of the lazily reduced 9 x 29-bit field (vimz_amd/csrc/fp29.hpp) on raw operands, per element on the device: a, b, c, d and out are HOST
+ * arrays of n slots of 9 words, limbs as they stand (no conversion on the way in or out; values of the 8 x 32 side in the first eight words; predicates
+ * write 0 / 1).  field = VIMZ_FIELD_*, op = the codes of vimz_amd/csrc/fp29_probe.hpp — the same function tests/native/fp29_probe_host.cpp runs on the
+ * host.  Operands must be inside the operation's contract (tests/_fp29_ref.py). */
+int vimz_test_fp29_probe(vimz_ctx* ctx, int field, int op, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d, uint32_t* out, size_t n);
+/* the fused products + cross term kernel of the verifier circuits' rows (k_spmv_cross16) on a caller's shape: rows [row0, row0 + nrows) of (A,B,C)·z into
+ * az, bz, cz and, when az1 is given, T = az1∘bz + az∘bz1 − u1·cz − u2·cz1 of those rows (az1 NULL = step 0: products only; T may then be NULL).  Every
+ * vector holds at least the shape's rows (z its columns); rows outside the range are left as they were. */
+int vimz_test_spmv_cross16(vimz_ctx* ctx, const vimz_r1cs* S, size_t row0, size_t nrows, const vimz_vec* z, vimz_vec* az, vimz_vec* bz, vimz_vec* cz,
+                           const vimz_vec* az1, const vimz_vec* bz1, const vimz_vec* cz1, const uint64_t u1[4], const uint64_t u2[4], int form, vimz_vec* T);
+/* k_cross_term over n elements with its boolean-row form: T as ever and, when Tm is given, the vector the dense MSM of a step takes — for i < nb twice T_i
+ * where az2_i is one, zero where it is zero, T_i + az1_i where it is anything else; T_i from nb on (instance 2 is the fresh one). */
+int vimz_test_cross_term_masked(vimz_ctx* ctx, size_t n, const vimz_vec* az1, const vimz_vec* bz1, const vimz_vec* cz1, const uint64_t u1[4], const vimz_vec* az2,
+                                const vimz_vec* bz2, const vimz_vec* cz2, const uint64_t u2[4], int form, vimz_vec* T, vimz_vec* Tm, size_t nb);
+
 #ifdef __cplusplus
 }
 #endif

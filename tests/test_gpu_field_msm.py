@@ -49,6 +49,28 @@ def test_field_ops_match_oracle(ctx, oracle, fid):
     assert inv == [pow(x, p - 2, p) for x in a[:64]]
 
 
+@pytest.mark.parametrize("fid", [0, 1, 2, 3])
+def test_field_ops_on_limb_patterns_match_python_integers(ctx, fid):
+    """The 8 x 32 Montgomery field on the device (vimz_field_op) on operands whose 32-bit limbs all come from {0, 1, 0x7fffffff, 0x80000000, 0xffffffff}
+    (reduced below p by clearing top bits): uniform, alternating, one limb different, random draws — the carry and borrow chains random operands
+    never build — for add / sub / mul / inv against Python integers."""
+    from tests._fp29_ref import word_patterns
+    p = MODULI[fid]
+    rng = random.Random(700 + fid)
+    pats = word_patterns(rng, p, n_random=1000)
+    assert len(pats) >= 1100 and all(0 <= x < p for x in pats) and {0, 1} <= set(pats)
+    a = pats + [pats[(7 * i + 3) % len(pats)] for i in range(len(pats))] + pats
+    b = pats[::-1] + pats + [rng.randrange(p) for _ in pats]
+    A, B = to_limbs(a), to_limbs(b)
+    for op, fn in (("add", lambda x, y: (x + y) % p), ("sub", lambda x, y: (x - y) % p), ("mul", lambda x, y: x * y % p)):
+        got = from_limbs(ctx.field_op(fid, op, A, B))
+        bad = [i for i in range(len(a)) if got[i] != fn(a[i], b[i])]
+        assert not bad, f"field {fid} {op}: {len(bad)} of {len(a)} differ, first a = {a[bad[0]]:#x} b = {b[bad[0]]:#x} got {got[bad[0]]:#x}"
+    inv = from_limbs(ctx.field_op(fid, "inv", to_limbs(pats)))
+    bad = [i for i, x in enumerate(pats) if inv[i] != pow(x, p - 2, p)]
+    assert not bad, f"field {fid} inv: {len(bad)} of {len(pats)} differ, first a = {pats[bad[0]]:#x} got {inv[bad[0]]:#x}"
+
+
 @pytest.mark.parametrize("cid", [0, 1, 2, 3])
 def test_group_law_matches_oracle(ctx, oracle, cid):
     r = MODULI[CURVE_SCALAR[cid]]

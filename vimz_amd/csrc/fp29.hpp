@@ -35,10 +35,15 @@ constexpr L29x9 ct_times29(const L29x9& x, uint32_t k) {      // k·x in 29-bit 
   return r;
 }
 
-// LAZY REDUCTION.  Nine 29-bit limbs hold integers below 2^261 = 128·2^254 > 128 p, seven bits more than a residue needs, and
-// the Montgomery product of x < Bx·p and y < By·p is below (Bx·By/128 + 1)·p (p/R' < 2^-7).  So values are kept as normalised
-// limbs (each < 2^29) of ANY representative below 128 p: `mul`/`sqr` never subtract p at the end (operand bounds must satisfy
-// Bx·By <= 64: result < 1.5 p), `add` only propagates carries, `sub<K>` computes a − b + K·p for a caller-stated K·p >= b.
+// LAZY REDUCTION.  Nine 29-bit limbs hold integers below 2^261, seven bits more than a residue needs, so values are kept as
+// normalised limbs (each < 2^29) of ANY representative below 2^261.
+//   Guaranteed: the Montgomery product of x and y is below x·y/2^261 + p (`redc` adds less than 2^261·p before it divides).
+//   Rounded form used in the formulas: x < Bx·p, y < By·p  ->  product below (Bx·By/128 + 1)·p.  Exact for BN254's two fields
+//   (p/2^261 < 2^-7).  For Pallas / Vesta p = 2^254 + 2^125..., so p/2^261 = 2^-7 + 2^-136 and the rounded form is short by less
+//   than Bx·By·2^-136 p — nothing a bound of a whole multiple of p/128 can notice.  For the same reason 2^261 is above 168 p for
+//   BN254 but just UNDER 128 p for Pallas / Vesta; no formula needs more than 64 p.
+// `mul`/`sqr` never subtract p at the end (operand bounds must satisfy Bx·By <= 64: result < 1.5 p), `add` only propagates
+// carries, `sub<K>` computes a − b + K·p for a caller-stated K·p >= b.
 // Every formula in ec.hpp carries its bounds in comments.  `canon()` brings a value below 8 p to [0, p) — needed only where
 // limbs are compared or leave this representation (to_std, table entries, equality) — and `is_zero_mod()` tests ≡ 0 (mod p)
 // of a value below 8 p in three instructions on the common path (k = v0·p^-1 mod 2^29 must be < 8 for v = k·p).
@@ -236,5 +241,11 @@ struct Fp29 {
     return r;
   }
 };
+
+template <class F> using R29 = Fp29<typename F::Params>;
+// x·2^256 (canonical, 8 words) -> x·2^261 in reduced radix: five modular doublings, then shifts and masks
+template <class F> VZ_HD R29<F> r29_of(const F& y) { F t = y; for (int k = 0; k < 5; k++) t = F::dbl(t); return R29<F>::pack(t.v); }
+// a sum of lazily reduced terms (anything below 2^261) back to 8 canonical words
+template <class F> VZ_HD F fe_of29(const R29<F>& a) { F r; a.weak_reduce().canon().unpack(r.v); return r; }
 
 }  // namespace vz

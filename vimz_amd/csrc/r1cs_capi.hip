@@ -262,3 +262,115 @@ int vimz_vec_axpy(vimz_ctx* ctx, vimz_vec* x1, const uint64_t r[4], int form, co
 }
 
 }  // extern "C"
+
+#ifdef VIMZ_TESTING
+// ---- test hooks (include/vimz_hip_testing.h): in libvimz_hip_testing.so only ----------------------------------------------------------------------
+#include "../../include/vimz_hip_testing.h"
+#include "fp29_probe.hpp"
+
+namespace {
+template <class P>
+__global__ void __launch_bounds__(256) k_fp29_probe(int op, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, const uint32_t* __restrict__ c,
+                                                    const uint32_t* __restrict__ d, uint32_t* __restrict__ out, size_t n) {
+  VZ_GRID_STRIDE(i, n) {
+    uint32_t x[4][FP29_PROBE_WORDS], r[FP29_PROBE_WORDS];
+    for (int k = 0; k < FP29_PROBE_WORDS; k++) { x[0][k] = a[FP29_PROBE_WORDS * i + k]; x[1][k] = b[FP29_PROBE_WORDS * i + k]; x[2][k] = c[FP29_PROBE_WORDS * i + k]; x[3][k] = d[FP29_PROBE_WORDS * i + k]; }
+    fp29_probe<P>(op, x[0], x[1], x[2], x[3], r);
+    for (int k = 0; k < FP29_PROBE_WORDS; k++) out[FP29_PROBE_WORDS * i + k] = r[k];
+  }
+}
+template <class F>
+int scalar_arg(vimz_ctx* ctx, const uint64_t* u, int form, F* out, const char* what) {
+  memcpy(out->v, u, 32);
+  if (!out->is_reduced()) return vz_fail(ctx, VIMZ_ERR_INVALID, what);
+  if (form == VIMZ_FORM_CANONICAL) *out = F::to_mont(*out);
+  return VIMZ_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int vimz_test_fp29_probe(vimz_ctx* ctx, int field, int op, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d, uint32_t* out, size_t n) {
+  if (!ctx || !a || !b || !c || !d || !out || field < 0 || field > 3) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_fp29_probe: bad argument");
+  {   // the operation must be one the probe knows (checked on the host, on a zero operand)
+    uint32_t zero[FP29_PROBE_WORDS] = {}, r[FP29_PROBE_WORDS];
+    if (fp29_probe<BnFr>(op, zero, zero, zero, zero, r)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_fp29_probe: unknown operation");
+  }
+  if (!n) return VIMZ_OK;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  R_TRY(hipSetDevice(ctx->device));
+  const size_t bytes = 4 * (size_t)FP29_PROBE_WORDS * n;
+  uint32_t* buf = nullptr;
+  R_TRY(hipMalloc((void**)&buf, 5 * bytes));
+  const uint32_t* src[4] = {a, b, c, d};
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < 4 && e == hipSuccess; k++) e = hipMemcpyAsync((char*)buf + k * bytes, src[k], bytes, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) {
+    uint32_t* p = buf; const size_t w = (size_t)FP29_PROBE_WORDS * n;
+    fp29_probe_field(field, [&](auto pp) {
+      typedef decltype(pp) P;
+      hipLaunchKernelGGL(k_fp29_probe<P>, dim3(stream_grid(n)), dim3(256), 0, ctx->stream, op, (const uint32_t*)p, (const uint32_t*)(p + w), (const uint32_t*)(p + 2 * w), (const uint32_t*)(p + 3 * w), p + 4 * w, n);
+      return 0;
+    });
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, (char*)buf + 4 * bytes, bytes, hipMemcpyDeviceToHost, ctx->stream);
+  const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+  hipFree(buf);
+  if (e != hipSuccess) return vz_fail(ctx, VIMZ_ERR_HIP, "vimz_test_fp29_probe", e);
+  if (e2 != hipSuccess) return vz_fail(ctx, VIMZ_ERR_HIP, "vimz_test_fp29_probe: synchronize", e2);
+  return VIMZ_OK;
+}
+
+int vimz_test_spmv_cross16(vimz_ctx* ctx, const vimz_r1cs* S, size_t row0, size_t nrows, const vimz_vec* z, vimz_vec* az, vimz_vec* bz, vimz_vec* cz,
+                           const vimz_vec* az1, const vimz_vec* bz1, const vimz_vec* cz1, const uint64_t u1[4], const uint64_t u2[4], int form, vimz_vec* T) {
+  if (!ctx || !S || !z || !az || !bz || !cz || !u1 || !u2) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spmv_cross16: bad argument");
+  if (az1 && (!bz1 || !cz1 || !T)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spmv_cross16: a running instance needs all of az1, bz1, cz1 and T");
+  if (row0 > S->nrows || nrows > S->nrows - row0) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spmv_cross16: rows outside the shape");
+  const vimz_vec* vs[7] = {az, bz, cz, az1, bz1, cz1, T};          // (indexed by absolute row)
+  for (const vimz_vec* v : vs) if (v && (v->field != S->field || v->n < S->nrows)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spmv_cross16: field or length of a vector does not fit the shape");
+  if (z->field != S->field || z->n < S->ncols) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spmv_cross16: z does not fit the shape");
+  if (!nrows) return VIMZ_OK;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  R_TRY(hipSetDevice(ctx->device));
+  int rc = field_dispatch(S->field, [&](auto f) {
+    typedef decltype(f) F;
+    F a, b; int r;
+    if ((r = scalar_arg(ctx, u1, form, &a, "vimz_test_spmv_cross16: u1 not below the modulus")) || (r = scalar_arg(ctx, u2, form, &b, "vimz_test_spmv_cross16: u2 not below the modulus"))) return r;
+    hipLaunchKernelGGL(k_spmv_cross16<F>, dim3((unsigned)((16 * nrows + 255) / 256)), dim3(256), 0, ctx->stream, S->M[0], S->M[1], S->M[2], (const uint32_t*)S->dict, (uint32_t)row0, (uint32_t)nrows,
+                       (const uint32_t*)z->d, az->d, bz->d, cz->d, az1 ? (const uint32_t*)az1->d : (const uint32_t*)nullptr, bz1 ? (const uint32_t*)bz1->d : (const uint32_t*)nullptr,
+                       cz1 ? (const uint32_t*)cz1->d : (const uint32_t*)nullptr, a, b, T ? T->d : (uint32_t*)nullptr);
+    return VIMZ_OK;
+  });
+  if (rc) return rc;
+  R_TRY(hipGetLastError());
+  R_TRY(hipStreamSynchronize(ctx->stream));
+  return VIMZ_OK;
+}
+
+int vimz_test_cross_term_masked(vimz_ctx* ctx, size_t n, const vimz_vec* az1, const vimz_vec* bz1, const vimz_vec* cz1, const uint64_t u1[4], const vimz_vec* az2, const vimz_vec* bz2,
+                                const vimz_vec* cz2, const uint64_t u2[4], int form, vimz_vec* T, vimz_vec* Tm, size_t nb) {
+  if (!ctx || !az1 || !bz1 || !cz1 || !az2 || !bz2 || !cz2 || !u1 || !u2 || !T) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_cross_term_masked: bad argument");
+  const vimz_vec* vs[8] = {az1, bz1, cz1, az2, bz2, cz2, T, Tm};
+  for (const vimz_vec* v : vs) if (v && (v->field != T->field || v->n < n)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_cross_term_masked: field or length of a vector");
+  if (nb > n || n >= (1ull << 32)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_cross_term_masked: nb beyond n");
+  if (T == Tm) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_cross_term_masked: T and Tm must differ");
+  if (!n) return VIMZ_OK;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  R_TRY(hipSetDevice(ctx->device));
+  int rc = field_dispatch(T->field, [&](auto f) {
+    typedef decltype(f) F;
+    F a, b; int r;
+    if ((r = scalar_arg(ctx, u1, form, &a, "vimz_test_cross_term_masked: u1 not below the modulus")) || (r = scalar_arg(ctx, u2, form, &b, "vimz_test_cross_term_masked: u2 not below the modulus"))) return r;
+    hipLaunchKernelGGL(k_cross_term<F>, dim3(stream_grid(n)), dim3(256), 0, ctx->stream, n, (const uint32_t*)az1->d, (const uint32_t*)bz1->d, (const uint32_t*)cz1->d, a,
+                       (const uint32_t*)az2->d, (const uint32_t*)bz2->d, (const uint32_t*)cz2->d, b, T->d, Tm ? Tm->d : (uint32_t*)nullptr, (uint32_t)nb);
+    return VIMZ_OK;
+  });
+  if (rc) return rc;
+  R_TRY(hipGetLastError());
+  R_TRY(hipStreamSynchronize(ctx->stream));
+  return VIMZ_OK;
+}
+
+}  // extern "C"
+#endif  // VIMZ_TESTING

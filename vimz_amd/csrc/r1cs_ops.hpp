@@ -26,11 +26,7 @@ inline std::vector<F> dict_for_device(const std::vector<F>& dict) {
   for (size_t i = 0; i < dict.size(); i++) { F t = dict[i]; out[2 * i] = t; for (int k = 0; k < 5; k++) t = F::dbl(t); out[2 * i + 1] = t; }
   return out;
 }
-template <class F> using R29 = Fp29<typename F::Params>;
-// x·2^256 (canonical, 8 words) -> x·2^261 in reduced radix: five modular doublings, then shifts and masks
-template <class F> __device__ __forceinline__ R29<F> r29_of(const F& y) { F t = y; for (int k = 0; k < 5; k++) t = F::dbl(t); return R29<F>::pack(t.v); }
-// a sum of lazily reduced terms back to 8 canonical words
-template <class F> __device__ __forceinline__ F fe_of29(const R29<F>& a) { F r; a.weak_reduce().canon().unpack(r.v); return r; }
+// (R29<F>, r29_of: x·2^256 -> x·2^261 in reduced radix, and fe_of29: a lazy sum back to 8 canonical words, live in fp29.hpp)
 
 constexpr uint32_t SPMV_LONG = 6;    // (matrix,row) items with more terms than this go to the wave-per-item kernel: the short
                                      // kernel's duration is its longest serial row (≈1 µs per dependent gather + multiply)

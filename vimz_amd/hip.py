@@ -1517,6 +1517,7 @@ class R1CSShape:
         lib.vimz_r1cs_free.argtypes = [vp, vp]
         lib.vimz_r1cs_free.restype = None
         lib.vimz_spmv3.argtypes = [vp, vp, vp, vp, vp, vp]
+        lib.vimz_r1cs_info.argtypes = [vp, vp]
         lib.vimz_commit_T.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int]
         keep, coos = [], []
         for rows, cols, vals in (A, B, Cm):
@@ -1542,21 +1543,30 @@ class R1CSShape:
             self.ctx.lib.vimz_r1cs_free(self.ctx.h, self.h)
             self.h = None
 
-    def multiply_vec(self, z):
-        """R1CSShape::multiply_vec: z a DeviceVec of ncols elements -> (Az, Bz, Cz) as new DeviceVecs."""
-        out = [self.ctx.vec_alloc(self.field, self.nrows) for _ in range(3)]
+    def multiply_vec(self, z, out=None):
+        """R1CSShape::multiply_vec: z a DeviceVec of ncols elements -> (Az, Bz, Cz), as new DeviceVecs or in the caller's three `out`
+        (each of at least nrows elements; what lies beyond nrows is left alone)."""
+        out = [self.ctx.vec_alloc(self.field, self.nrows) for _ in range(3)] if out is None else list(out)
         self.ctx._chk(self.ctx.lib.vimz_spmv3(self.ctx.h, self.h, z.h, out[0].h, out[1].h, out[2].h))
         return out
 
-    def commit_T(self, ck, z1, u1, z2, u2=1):
-        """R1CSShape::commit_T: returns (T DeviceVec of nrows elements, comm_T as (8,) uint64 canonical affine)."""
-        T = self.ctx.vec_alloc(self.field, self.nrows)
+    def commit_T(self, ck, z1, u1, z2, u2=1, out=None, form=L.FORM_CANONICAL):
+        """R1CSShape::commit_T: returns (T DeviceVec of nrows elements — a new one, or the caller's `out` — and comm_T as (8,) uint64
+        canonical affine); u1, u2 integers in `form`."""
+        T = self.ctx.vec_alloc(self.field, self.nrows) if out is None else out
         lim = lambda x: np.array([(int(x) >> (64 * k)) & 0xFFFFFFFFFFFFFFFF for k in range(4)], dtype=np.uint64)
         a, b = lim(u1), lim(u2)
-        out = np.zeros(8, dtype=np.uint64)
+        res = np.zeros(8, dtype=np.uint64)
         try:
-            self.ctx._chk(self.ctx.lib.vimz_commit_T(self.ctx.h, self.h, ck.h, z1.h, _ptr(a), z2.h, _ptr(b), L.FORM_CANONICAL, T.h, _ptr(out), L.FORM_CANONICAL))
+            self.ctx._chk(self.ctx.lib.vimz_commit_T(self.ctx.h, self.h, ck.h, z1.h, _ptr(a), z2.h, _ptr(b), form, T.h, _ptr(res), L.FORM_CANONICAL))
         except Exception:
-            T.free()
+            if out is None:
+                T.free()
             raise
-        return T, out
+        return T, res
+
+    def info(self):
+        """vimz_r1cs_info: rows, columns, non-zeros of A, B, C, dictionary size, long (matrix, row) items, field."""
+        a = np.zeros(8, dtype=np.uint64)
+        self.ctx._chk(self.ctx.lib.vimz_r1cs_info(self.h, _ptr(a)))
+        return dict(zip(("nrows", "ncols", "nnz_a", "nnz_b", "nnz_c", "dict", "n_long", "field"), (int(x) for x in a)))
