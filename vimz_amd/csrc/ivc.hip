@@ -22,6 +22,13 @@
 
 namespace {
 
+// bit length of a canonical scalar (0 for zero): the running u of an unbroken chain is 1 + Σ rho_k, far below 2^254, and a double-and-add over
+// its leading zero bits only doubles the identity
+int scalar_bits(const uint32_t* k) {
+  for (int i = 7; i >= 0; i--) if (k[i]) return 32 * i + 32 - __builtin_clz(k[i]);
+  return 0;
+}
+
 // read the results of the queued secondary MSMs (comm_W of the fresh instance, comm_T of its fold)
 int finish_secondary(vimz_ivc* v) {
   if (!v->pending_sec) return VIMZ_OK;
@@ -251,7 +258,7 @@ int ivc_fold_core(vimz_ivc* v, const uint64_t* step_inputs, const uint64_t* witn
         S1_row = to_affine(ones_finish<BnG1>((const char*)bb.pin + r * pin_stride + vimz_prover::S1_SLOT));
         auto& sl = v->t1[i & 1];
         if (i > 0 && sl.step == (int64_t)i && sl.tricked) {
-          if (!aff_is_identity(S1_row)) { const Fe uc = Fe::from_mont(sl.u_at); boolCorr = scalar_mul(S1_row, uc.v, 254); }
+          if (!aff_is_identity(S1_row)) { const Fe uc = Fe::from_mont(sl.u_at); boolCorr = scalar_mul(S1_row, uc.v, scalar_bits(uc.v)); }
           G1 nca = sl.ca_at; if (!nca.is_identity()) nca.Y = Fq::neg(nca.Y);
           add_full(boolCorr, nca);
         }
@@ -288,7 +295,7 @@ int ivc_fold_core(vimz_ivc* v, const uint64_t* step_inputs, const uint64_t* witn
           auto& sl = v->t1[i & 1];
           if (sl.tricked) {      // (its completion: u·S_1(row i) − C_A as they are now)
             boolCorr = G1::identity();
-            if (!aff_is_identity(S1_row)) { const Fe uc = Fe::from_mont(sl.u_at); boolCorr = scalar_mul(S1_row, uc.v, 254); }
+            if (!aff_is_identity(S1_row)) { const Fe uc = Fe::from_mont(sl.u_at); boolCorr = scalar_mul(S1_row, uc.v, scalar_bits(uc.v)); }
             G1 nca = sl.ca_at; if (!nca.is_identity()) nca.Y = Fq::neg(nca.Y);
             add_full(boolCorr, nca);
           }

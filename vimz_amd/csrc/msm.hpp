@@ -43,7 +43,11 @@ namespace vz {
 // every bucket is then added into half of the 14 planes: 131 k full additions instead of 32 k, a tenth of the accumulation's work on top — and inside
 // a fold, where the GPU is busy throughout, that costs more than the shorter tail gains: 1 176 against 1 198 steps/s over 256 rows, 936 against 938 in
 // the 20-row window, one chain 829 against 822 (round 5, same box, profiles/r05_reduce_planes.txt).
-struct MsmTuning { int sort_blocks = 0, combine_lane_bits = -1, small_lean = 0, witness_sub = 0, ones_dense = 1, reduce_planes = 0, accum_lds_kb = 0, dense_sub = 0; };
+// signed_scalars (1: on, the default): a scalar above (p − 1)/2 enters every digit producer as p − s with the signs of its digits flipped (load_scalar).  The
+// cross term's vector is mostly p − (small): dense 254-bit numbers whose upper windows all spell the upper part of p — 17 digits at c = 15, seven of them
+// the same for every such scalar (seven buckets of tens of thousands of entries each) — where the small value has 9-10 digits and empty upper windows.
+// 0 keeps the plain recoding in the binary for A/B runs and for the schedule-independence tests; the commitment is the same group element either way.
+struct MsmTuning { int sort_blocks = 0, combine_lane_bits = -1, small_lean = 0, witness_sub = 0, ones_dense = 1, reduce_planes = 0, accum_lds_kb = 0, dense_sub = 0, signed_scalars = 1; };
 inline const MsmTuning& msm_tuning() {
   static const MsmTuning t = [] {
     MsmTuning r;
@@ -55,6 +59,7 @@ inline const MsmTuning& msm_tuning() {
       if (const char* q = strstr(e, "dense_sub=")) { const int v = atoi(q + 10); if (v >= 2 && v <= MSM_SUB) r.dense_sub = v; }
       if (const char* q = strstr(e, "ones_dense=")) r.ones_dense = atoi(q + 11);
       if (const char* q = strstr(e, "reduce_planes=")) r.reduce_planes = atoi(q + 14);
+      if (const char* q = strstr(e, "signed_scalars=")) r.signed_scalars = atoi(q + 15) != 0;
       if (const char* q = strstr(e, "accum_lds_kb=")) { const int v = atoi(q + 13); if (v >= 0 && v <= 160) r.accum_lds_kb = v; }
     }
     return r;
@@ -74,8 +79,11 @@ __device__ __forceinline__ uint32_t window_bits(const uint32_t* s, int lo, int c
 }
 
 // returns false when the scalar is to be skipped (zero, or the unit when `skip_ones`: units are summed by k_ones_partial)
+// sgn: a canonical value above (p − 1)/2 comes back as p − s with flip = 1 — the caller negates every digit (s·P = (p − s)·(−P)); histogram and scatter
+// both decide HERE, so they cannot disagree.  from_mont returns a value below p for all four scalar fields (a Montgomery product by 1 is below p + 1 before
+// its conditional subtraction); of mont == 0 input the callers promise the same, and a word above p is left as it is, as without sgn.
 template <class S>
-__device__ __forceinline__ bool load_scalar(const uint32_t* __restrict__ scalars, size_t i, int mont, int skip_ones, uint32_t* s) {
+__device__ __forceinline__ bool load_scalar(const uint32_t* __restrict__ scalars, size_t i, int mont, int skip_ones, int sgn, uint32_t* s, uint32_t& flip) {
   const uint4* p = reinterpret_cast<const uint4*>(scalars + 8 * i);
   uint4 a = p[0], b = p[1];
   S x;
@@ -88,14 +96,28 @@ __device__ __forceinline__ bool load_scalar(const uint32_t* __restrict__ scalars
     if (one) return false;
   }
   if (mont) x = S::from_mont(x);
+  flip = 0;
+  if (sgn) {
+    // t = p − s;  s > (p − 1)/2  <=>  t < s  (p is odd);  a borrow out of t: s > p, not a canonical value
+    uint32_t t[8]; uint64_t br = 0, lt = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) { const uint64_t d = (uint64_t)S::Params::MOD.w[k] - x.v[k] - br; t[k] = (uint32_t)d; br = (d >> 32) & 1; }
+#pragma unroll
+    for (int k = 0; k < 8; k++) { const uint64_t d = (uint64_t)t[k] - x.v[k] - lt; lt = (d >> 32) & 1; }
+    if (!br && lt) {
+      flip = 1;
+#pragma unroll
+      for (int k = 0; k < 8; k++) x.v[k] = t[k];
+    }
+  }
 #pragma unroll
   for (int k = 0; k < 8; k++) s[k] = x.v[k];
   return true;
 }
 
-// Calls f(window, bucket_index_in_window, negative) for every non-zero signed digit.
+// Calls f(window, bucket_index_in_window, negative) for every non-zero signed digit (flip: load_scalar's — the digits of −s).
 template <class Fn>
-__device__ __forceinline__ void for_each_digit(const uint32_t* s, int c, int K, Fn f) {
+__device__ __forceinline__ void for_each_digit(const uint32_t* s, int c, int K, uint32_t flip, Fn f) {
   uint32_t carry = 0;
   const uint32_t half = 1u << (c - 1);
   for (int w = 0; w < K; w++) {
@@ -103,7 +125,7 @@ __device__ __forceinline__ void for_each_digit(const uint32_t* s, int c, int K, 
     uint32_t neg = d > half;
     uint32_t mag = neg ? (1u << c) - d : d;
     carry = neg;
-    if (mag) f(w, mag - 1, neg);
+    if (mag) f(w, mag - 1, neg ^ flip);
   }
 }
 
@@ -133,12 +155,12 @@ __device__ __forceinline__ uint32_t agg_atomic_inc(uint32_t* __restrict__ ctr, u
 }
 
 template <class S>
-__global__ void k_hist(const uint32_t* __restrict__ scalars, size_t n, int mont, int skip_ones, int c, int K, uint32_t nbw /* bucket stride per window: 2^(c-1), or 0 with window tables */,
+__global__ void k_hist(const uint32_t* __restrict__ scalars, size_t n, int mont, int skip_ones, int sgn, int c, int K, uint32_t nbw /* bucket stride per window: 2^(c-1), or 0 with window tables */,
                        uint32_t* __restrict__ counts) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    uint32_t s[8];
-    if (!load_scalar<S>(scalars, i, mont, skip_ones, s)) continue;
-    for_each_digit(s, c, K, [&](int w, uint32_t b, uint32_t) { agg_atomic_inc(counts, (uint32_t)w * nbw + b); });
+    uint32_t s[8], flip;
+    if (!load_scalar<S>(scalars, i, mont, skip_ones, sgn, s, flip)) continue;
+    for_each_digit(s, c, K, flip, [&](int w, uint32_t b, uint32_t) { agg_atomic_inc(counts, (uint32_t)w * nbw + b); });
   }
 }
 
@@ -183,14 +205,14 @@ __global__ void __launch_bounds__(1024) k_scan(const uint32_t* __restrict__ coun
 }
 
 template <class S>
-__global__ void k_scatter(const uint32_t* __restrict__ scalars, size_t n, int mont, int skip_ones, int c, int K, uint32_t nbw,
+__global__ void k_scatter(const uint32_t* __restrict__ scalars, size_t n, int mont, int skip_ones, int sgn, int c, int K, uint32_t nbw,
                           uint32_t pt_stride /* 0, or the table row length: entry = window * pt_stride + point */,
                           const uint32_t* __restrict__ bucket_off, uint32_t* __restrict__ cursor,
                           uint32_t* __restrict__ sorted) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    uint32_t s[8];
-    if (!load_scalar<S>(scalars, i, mont, skip_ones, s)) continue;
-    for_each_digit(s, c, K, [&](int w, uint32_t b, uint32_t neg) {
+    uint32_t s[8], flip;
+    if (!load_scalar<S>(scalars, i, mont, skip_ones, sgn, s, flip)) continue;
+    for_each_digit(s, c, K, flip, [&](int w, uint32_t b, uint32_t neg) {
       uint32_t g = (uint32_t)w * nbw + b;
       uint32_t pos = bucket_off[g] + agg_atomic_inc(cursor, g);
       sorted[pos] = ((uint32_t)i + (uint32_t)w * pt_stride) | (neg << 31);
@@ -210,7 +232,7 @@ constexpr uint32_t SORT_BLOCKS = 256;      // at most one workgroup per CU (msm_
 constexpr uint32_t SORT_THREADS = 1024;
 
 template <class S>
-__global__ void __launch_bounds__(SORT_THREADS) k_hist_lds(const uint32_t* __restrict__ scalars, size_t n, int mont, int skip_ones, int c, int K,
+__global__ void __launch_bounds__(SORT_THREADS) k_hist_lds(const uint32_t* __restrict__ scalars, size_t n, int mont, int skip_ones, int sgn, int c, int K,
                                                            uint32_t nbw, uint32_t nb, uint32_t* __restrict__ block_hist /* [SORT_BLOCKS][nb] */) {
   extern __shared__ uint32_t lds_cnt[];
   for (uint32_t g = threadIdx.x; g < nb; g += SORT_THREADS) lds_cnt[g] = 0;
@@ -218,9 +240,9 @@ __global__ void __launch_bounds__(SORT_THREADS) k_hist_lds(const uint32_t* __res
   const size_t chunk = (n + gridDim.x - 1) / gridDim.x;
   const size_t lo = blockIdx.x * chunk, hi = lo + chunk < n ? lo + chunk : n;
   for (size_t i = lo + threadIdx.x; i < hi; i += SORT_THREADS) {
-    uint32_t s[8];
-    if (!load_scalar<S>(scalars, i, mont, skip_ones, s)) continue;
-    for_each_digit(s, c, K, [&](int w, uint32_t b, uint32_t) { atomicAdd(&lds_cnt[(uint32_t)w * nbw + b], 1u); });
+    uint32_t s[8], flip;
+    if (!load_scalar<S>(scalars, i, mont, skip_ones, sgn, s, flip)) continue;
+    for_each_digit(s, c, K, flip, [&](int w, uint32_t b, uint32_t) { atomicAdd(&lds_cnt[(uint32_t)w * nbw + b], 1u); });
   }
   __syncthreads();
   uint32_t* out = block_hist + (size_t)blockIdx.x * nb;
@@ -259,7 +281,7 @@ __global__ void __launch_bounds__(1024) k_prefix_scan(uint32_t* __restrict__ blo
 }
 
 template <class S>
-__global__ void __launch_bounds__(SORT_THREADS) k_scatter_lds(const uint32_t* __restrict__ scalars, size_t n, int mont, int skip_ones, int c, int K,
+__global__ void __launch_bounds__(SORT_THREADS) k_scatter_lds(const uint32_t* __restrict__ scalars, size_t n, int mont, int skip_ones, int sgn, int c, int K,
                                                               uint32_t nbw, uint32_t nb, uint32_t pt_stride, const uint32_t* __restrict__ bucket_off,
                                                               const uint32_t* __restrict__ block_hist, uint32_t* __restrict__ sorted) {
   extern __shared__ uint32_t lds_pos[];
@@ -269,9 +291,9 @@ __global__ void __launch_bounds__(SORT_THREADS) k_scatter_lds(const uint32_t* __
   const size_t chunk = (n + gridDim.x - 1) / gridDim.x;
   const size_t lo = blockIdx.x * chunk, hi = lo + chunk < n ? lo + chunk : n;
   for (size_t i = lo + threadIdx.x; i < hi; i += SORT_THREADS) {
-    uint32_t s[8];
-    if (!load_scalar<S>(scalars, i, mont, skip_ones, s)) continue;
-    for_each_digit(s, c, K, [&](int w, uint32_t b, uint32_t neg) {
+    uint32_t s[8], flip;
+    if (!load_scalar<S>(scalars, i, mont, skip_ones, sgn, s, flip)) continue;
+    for_each_digit(s, c, K, flip, [&](int w, uint32_t b, uint32_t neg) {
       const uint32_t pos = atomicAdd(&lds_pos[(uint32_t)w * nbw + b], 1u);
       sorted[pos] = ((uint32_t)i + (uint32_t)w * pt_stride) | (neg << 31);
     });
@@ -599,7 +621,7 @@ __device__ __forceinline__ int signed_digit(const uint32_t* s, int w) {
 }
 
 template <class S, class F, int LEAN /* the option small_lean: its code is only in the instantiations that run it */>
-__global__ void __launch_bounds__(SMALL_THREADS) k_msm_small(const uint32_t* __restrict__ bases, const uint32_t* __restrict__ scalars, uint32_t n, int mont,
+__global__ void __launch_bounds__(SMALL_THREADS) k_msm_small(const uint32_t* __restrict__ bases, const uint32_t* __restrict__ scalars, uint32_t n, int mont, int sgn,
                                                    uint32_t Q, uint32_t chunk, uint32_t* __restrict__ chunk_out /* K*Q points */,
                                                    uint32_t* __restrict__ done /* K counters, zero between launches; nullptr: k_msm_small_sum follows */,
                                                    uint32_t* __restrict__ window_sums,
@@ -624,9 +646,10 @@ __global__ void __launch_bounds__(SMALL_THREADS) k_msm_small(const uint32_t* __r
     dig[k] = 0;
     const uint32_t i = lo + t + SMALL_THREADS * k;
     if (i < hi) {
-      uint32_t sc[8];
-      if (load_scalar<S>(scalars, i, mont, 0, sc)) {
+      uint32_t sc[8], flip;
+      if (load_scalar<S>(scalars, i, mont, 0, sgn, sc, flip)) {
         dig[k] = signed_digit<SMALL_C>(sc, (int)w);
+        if (flip) dig[k] = -dig[k];
         if (dig[k]) atomicAdd(&cnt[(dig[k] < 0 ? -dig[k] : dig[k]) - 1], 1u);
       }
     }
@@ -823,7 +846,7 @@ hipError_t build_multiples(hipStream_t stream, const uint32_t* d_tables, size_t 
 
 // grid (Q, K): workgroup (q, w) sums the points selected by window w's digits of scalars [q·FIXED_CHUNK, (q+1)·FIXED_CHUNK).
 template <class S, class F>
-__global__ void __launch_bounds__(256) k_msm_fixed(const uint32_t* __restrict__ mult, uint32_t tstride, const uint32_t* __restrict__ scalars, uint32_t n, int mont,
+__global__ void __launch_bounds__(256) k_msm_fixed(const uint32_t* __restrict__ mult, uint32_t tstride, const uint32_t* __restrict__ scalars, uint32_t n, int mont, int sgn,
                                                    uint32_t Q, uint32_t* __restrict__ partial /* K x Q */, uint32_t* __restrict__ done /* K counters */,
                                                    uint32_t* __restrict__ window_sums) {
   __shared__ XYZZ<F> sh[256];
@@ -839,9 +862,9 @@ __global__ void __launch_bounds__(256) k_msm_fixed(const uint32_t* __restrict__ 
     const uint32_t i = q * FIXED_CHUNK + t + 256u * k;
     have[k] = false; neg[k] = false;
     if (i < n) {
-      uint32_t sc[8];
-      if (load_scalar<S>(scalars, i, mont, 0, sc)) {
-        const int d = signed_digit<SMALL_C>(sc, (int)w);
+      uint32_t sc[8], flip;
+      if (load_scalar<S>(scalars, i, mont, 0, sgn, sc, flip)) {
+        const int d = flip ? -signed_digit<SMALL_C>(sc, (int)w) : signed_digit<SMALL_C>(sc, (int)w);
         if (d) {
           have[k] = true; neg[k] = d < 0;
           const uint32_t m = (uint32_t)(d < 0 ? -d : d) - 1u;
@@ -936,6 +959,7 @@ hipError_t msm_launch(hipStream_t stream, MsmWorkspace& ws, const uint32_t* d_ba
   typedef typename C::Coord F;
   typedef typename C::Scalar S;
   if (n == 0 || n >= (1u << 31)) return hipErrorInvalidValue;
+  const int sgn = msm_tuning().signed_scalars;
   // The window sums go straight into the caller's pinned buffer (host memory the device can write): the copy that used to follow —
   // a launch and a dependent hop between the last kernel and the host's wake-up — is gone.
   constexpr bool direct = true;
@@ -959,7 +983,7 @@ hipError_t msm_launch(hipStream_t stream, MsmWorkspace& ws, const uint32_t* d_ba
       const uint32_t Qf = (uint32_t)((n + FIXED_CHUNK - 1) / FIXED_CHUNK);
       if (ev) for (int i = 0; i < 4; i++) VZ_HIP_CHECK(hipEventRecord(ev[i], stream));
       hipLaunchKernelGGL((k_msm_fixed<S, F>), dim3(Qf, ps.K), dim3(256), 0, stream, tb->mult + (size_t)AFFINE_WORDS * SMALL_NBW * tb->offset, (uint32_t)tb->n_total, d_scalars, (uint32_t)n,
-                         scalars_mont, Qf, chunk_out, done, direct ? reinterpret_cast<uint32_t*>(pinned_dst) : reinterpret_cast<uint32_t*>(ws.window_sums));
+                         scalars_mont, sgn, Qf, chunk_out, done, direct ? reinterpret_cast<uint32_t*>(pinned_dst) : reinterpret_cast<uint32_t*>(ws.window_sums));
       if (ev) for (int i = 4; i < 7; i++) VZ_HIP_CHECK(hipEventRecord(ev[i], stream));
       VZ_HIP_CHECK(hipGetLastError());
       if (!direct) VZ_HIP_CHECK(hipMemcpyAsync(pinned_dst, ws.window_sums, 4 * (size_t)XYZZ_WORDS * ps.K, hipMemcpyDeviceToHost, stream));
@@ -967,7 +991,7 @@ hipError_t msm_launch(hipStream_t stream, MsmWorkspace& ws, const uint32_t* d_ba
     }
     if (ev) for (int i = 0; i < 4; i++) VZ_HIP_CHECK(hipEventRecord(ev[i], stream));
     static const bool sum_kernel = getenv("VIMZ_DEBUG_SMALL_SUM_KERNEL") != nullptr;
-#define VZ_SMALL(LEAN) hipLaunchKernelGGL((k_msm_small<S, F, LEAN>), dim3(ps.K, Q), dim3(SMALL_THREADS), 0, stream, d_bases, d_scalars, (uint32_t)n, scalars_mont, Q, chunk, chunk_out, \
+#define VZ_SMALL(LEAN) hipLaunchKernelGGL((k_msm_small<S, F, LEAN>), dim3(ps.K, Q), dim3(SMALL_THREADS), 0, stream, d_bases, d_scalars, (uint32_t)n, scalars_mont, sgn, Q, chunk, chunk_out, \
                        sum_kernel ? (uint32_t*)nullptr : done, direct ? reinterpret_cast<uint32_t*>(pinned_dst) : reinterpret_cast<uint32_t*>(ws.window_sums), \
                        small_tb ? tb->d + (size_t)AFFINE_WORDS * tb->offset : (const uint32_t*)nullptr, small_tb ? (uint32_t)tb->n_total : 0u)
     switch (msm_tuning().small_lean) { case 0: VZ_SMALL(0); break; case 1: VZ_SMALL(1); break; default: VZ_SMALL(2); break; }
@@ -1041,9 +1065,9 @@ hipError_t msm_launch(hipStream_t stream, MsmWorkspace& ws, const uint32_t* d_ba
         attr_devices |= 1ull << (dev & 63);
       }
     }
-    hipLaunchKernelGGL(k_hist_lds<S>, dim3(sort_blocks), dim3(SORT_THREADS), pl.nb * 4, stream, d_scalars, n, scalars_mont, split_ones, pl.c, pl.K, bstride, pl.nb, ws.block_hist);
+    hipLaunchKernelGGL(k_hist_lds<S>, dim3(sort_blocks), dim3(SORT_THREADS), pl.nb * 4, stream, d_scalars, n, scalars_mont, split_ones, sgn, pl.c, pl.K, bstride, pl.nb, ws.block_hist);
   } else {
-    hipLaunchKernelGGL(k_hist<S>, dim3(gs), dim3(TB), 0, stream, d_scalars, n, scalars_mont, split_ones, pl.c, pl.K, bstride, ws.counts);
+    hipLaunchKernelGGL(k_hist<S>, dim3(gs), dim3(TB), 0, stream, d_scalars, n, scalars_mont, split_ones, sgn, pl.c, pl.K, bstride, ws.counts);
   }
   VZ_EV(1);
   // lanes per ordinary bucket in k_combine, from the mean number of partials per bucket (upper bound: every digit non-zero): two
@@ -1062,10 +1086,10 @@ hipError_t msm_launch(hipStream_t stream, MsmWorkspace& ws, const uint32_t* d_ba
     hipLaunchKernelGGL(k_scan<MSM_SUB>, dim3(1), dim3(1024), 0, stream, ws.counts, pl.nb, ws.bucket_off, ws.sub_off, ws.totals, sub, ws.heavy, heavy_min, MsmWorkspace::HEAVY_CAP);
   VZ_EV(2);
   if (lds_sort)
-    hipLaunchKernelGGL(k_scatter_lds<S>, dim3(sort_blocks), dim3(SORT_THREADS), pl.nb * 4, stream, d_scalars, n, scalars_mont, split_ones, pl.c, pl.K, bstride, pl.nb,
+    hipLaunchKernelGGL(k_scatter_lds<S>, dim3(sort_blocks), dim3(SORT_THREADS), pl.nb * 4, stream, d_scalars, n, scalars_mont, split_ones, sgn, pl.c, pl.K, bstride, pl.nb,
                        pstride, ws.bucket_off, ws.block_hist, ws.sorted);
   else
-    hipLaunchKernelGGL(k_scatter<S>, dim3(gs), dim3(TB), 0, stream, d_scalars, n, scalars_mont, split_ones, pl.c, pl.K, bstride, pstride,
+    hipLaunchKernelGGL(k_scatter<S>, dim3(gs), dim3(TB), 0, stream, d_scalars, n, scalars_mont, split_ones, sgn, pl.c, pl.K, bstride, pstride,
                        ws.bucket_off, ws.cursor, ws.sorted);
   VZ_EV(3);
   uint32_t* partial = reinterpret_cast<uint32_t*>(ws.partial);
