@@ -72,6 +72,10 @@ int vimz_trace_marker(vimz_ctx* ctx, int id);
  * the number for every later call of this process (0: every row's witness entirely on the GPU), -1 restores the library's policy (24 for calls of at
  * most 24 rows — for the segments of one proof: proofs of at most 28 rows in all — on six or more host cores, else 0).  Returns the previous setting. */
 long vimz_set_head_rows(long rows);
+/* Row groups of the batch producer: the most rows of a batch whose witness commitments (and S_1 sums) are issued as ONE chain of kernel launches, the row in a
+ * grid dimension (the proof is bit-identical whatever the value): rows >= 0 pins it for every later call of this process (0 or 1: one chain per row; at most 16),
+ * -1 restores the default (4, or VIMZ_TUNE's rows_group).  Returns the previous setting. */
+long vimz_set_rows_group(long rows);
 /* A fingerprint of the host a benchmark line was measured on: out[0] = µs per Poseidon permutation (t = 9) on one host core, out[1] = µs per
  * empty kernel launch + stream synchronise (median of 200), out[2] = host cores this process may use, out[3] = µs per event record + synchronise. */
 int vimz_host_fingerprint(vimz_ctx* ctx, double out[4]);

@@ -63,6 +63,13 @@ int vimz_test_spmv_cross16(vimz_ctx* ctx, const vimz_r1cs* S, size_t row0, size_
  * where az2_i is one, zero where it is zero, T_i + az1_i where it is anything else; T_i from nb on (instance 2 is the fresh one). */
 int vimz_test_cross_term_masked(vimz_ctx* ctx, size_t n, const vimz_vec* az1, const vimz_vec* bz1, const vimz_vec* cz1, const uint64_t u1[4], const vimz_vec* az2,
                                 const vimz_vec* bz2, const vimz_vec* cz2, const uint64_t u2[4], int form, vimz_vec* T, vimz_vec* Tm, size_t nb);
+/* msm_launch_rows (vimz_amd/csrc/msm.hpp) on a caller's rows: G (<= 16) vectors of n scalars each, row r at scalars + 4·r·row_stride words of 64 bits (host;
+ * form = VIMZ_FORM_*), committed over the first n points of a BN254 G1 key as ONE chain of launches with the unit scalars split off — with the key's shared-bucket
+ * window tables (use_tables != 0; vimz_bases_precompute first) or without — `calls` times over on ONE fresh workspace.  out_xy: calls·G affine points
+ * (canonical, 8 words each, the identity as zeros), call after call.  n_ones != 0: every row's unit sum over its first n_ones scalars rides along as the
+ * producer's S_1 sums do (s1_xy, calls·G points) and is computed again by one ones_launch per row (s1_ref_xy, G points). */
+int vimz_test_msm_rows(vimz_ctx* ctx, const vimz_bases* bases, const uint64_t* scalars, size_t n, size_t row_stride, size_t G, int form, int use_tables,
+                       size_t n_ones, int calls, uint64_t* out_xy, uint64_t* s1_xy, uint64_t* s1_ref_xy);
 
 #ifdef __cplusplus
 }

@@ -555,3 +555,51 @@ int vimz_curve_add(vimz_ctx* c, int curve, const uint64_t* p, const uint64_t* q,
 }
 
 }  // extern "C"
+
+#ifdef VIMZ_TESTING
+// ---- test hook (include/vimz_hip_testing.h): in libvimz_hip_testing.so only ----------------------------------------------------------------------
+#include "../../include/vimz_hip_testing.h"
+extern "C" int vimz_test_msm_rows(vimz_ctx* c, const vimz_bases* bases, const uint64_t* scalars, size_t n, size_t row_stride, size_t G, int form, int use_tables,
+                                  size_t n_ones, int calls, uint64_t* out_xy, uint64_t* s1_xy, uint64_t* s1_ref_xy) {
+  if (!c || !bases || !scalars || !out_xy || !n || !G || G > MSM_ROWS_MAX || row_stride < n || n > bases->n || n_ones > n || calls < 1 || bases->curve != VIMZ_CURVE_BN254_G1 ||
+      (n_ones && (!s1_xy || !s1_ref_xy)) || (use_tables && !bases->tables))
+    return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_rows: bad argument");
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  typedef BnG1::Base FS;
+  const size_t pin_stride = 4 * (size_t)XYZZ_WORDS * MSM_MAX_WINDOWS, s1_slot = 4 * (size_t)XYZZ_WORDS * (MSM_MAX_WINDOWS - 1);
+  const int mont = form == VIMZ_FORM_MONTGOMERY;
+  int rc = ensure_scratch(c, 32 * G * row_stride); if (rc) return rc;
+  char* pin = nullptr;
+  MsmWorkspace ws;
+  hipError_t e = hipHostMalloc((void**)&pin, G * pin_stride);
+  if (e == hipSuccess) e = hipMemcpyAsync(c->scratch, scalars, 32 * ((G - 1) * row_stride + n), hipMemcpyHostToDevice, c->stream);
+  const uint32_t* ds = (const uint32_t*)c->scratch;
+  const BaseTables tb = bases->tb(0);
+  auto affine_out = [&](const Affine<FS>& a, uint64_t* o) { const FS x = FS::from_mont(a.x), y = FS::from_mont(a.y); memcpy(o, x.v, 32); memcpy(o + 4, y.v, 32); };
+  for (int call = 0; call < calls && e == hipSuccess; call++) {
+    memset(pin, 0xff, G * pin_stride);      // (nothing of an earlier call may pass for this one's result)
+    OnesDesc s1[MSM_ROWS_MAX];
+    for (size_t r = 0; r < G; r++) s1[r] = OnesDesc{ds + 8 * r * row_stride, bases->d, reinterpret_cast<uint32_t*>(pin + r * pin_stride + s1_slot), n_ones};
+    MsmPlan pl;
+    e = msm_launch_rows<BnG1>(c->stream, ws, bases->d, ds, n, row_stride, (uint32_t)G, mont, pin, pin_stride, &pl, 1, use_tables ? &tb : nullptr, s1, n_ones ? (uint32_t)G : 0u, (uint32_t)G);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) break;
+    for (size_t r = 0; r < G; r++) {
+      affine_out(msm_finish<BnG1>(pl, pin + r * pin_stride), out_xy + 8 * ((size_t)call * G + r));
+      if (n_ones) affine_out(to_affine(ones_finish<BnG1>(pin + r * pin_stride + s1_slot)), s1_xy + 8 * ((size_t)call * G + r));
+    }
+  }
+  for (size_t r = 0; r < G && n_ones && e == hipSuccess; r++) {      // the same sums by the per-row launches
+    memset(pin, 0xff, 4 * (size_t)XYZZ_WORDS);
+    e = ones_launch<BnG1>(c->stream, ws, bases->d, ds + 8 * r * row_stride, n_ones, mont, pin);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) affine_out(to_affine(ones_finish<BnG1>(pin)), s1_ref_xy + 8 * r);
+  }
+  hipStreamSynchronize(c->stream);
+  ws.release();
+  if (pin) hipHostFree(pin);
+  if (e != hipSuccess) return vz_fail(c, VIMZ_ERR_HIP, "vimz_test_msm_rows", e);
+  return VIMZ_OK;
+}
+#endif  // VIMZ_TESTING

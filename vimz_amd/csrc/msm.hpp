@@ -47,6 +47,7 @@ namespace vz {
 // cross term's vector is mostly p − (small): dense 254-bit numbers whose upper windows all spell the upper part of p — 17 digits at c = 15, seven of them
 // the same for every such scalar (seven buckets of tens of thousands of entries each) — where the small value has 9-10 digits and empty upper windows.
 // 0 keeps the plain recoding in the binary for A/B runs and for the schedule-independence tests; the commitment is the same group element either way.
+// (rows_group, a key of the same variable, is the batch producer's: prover_internal.hpp, rows_group_wanted.)
 struct MsmTuning { int sort_blocks = 0, combine_lane_bits = -1, small_lean = 0, witness_sub = 0, ones_dense = 1, reduce_planes = 0, accum_lds_kb = 0, dense_sub = 0, signed_scalars = 1; };
 inline const MsmTuning& msm_tuning() {
   static const MsmTuning t = [] {
@@ -233,8 +234,9 @@ constexpr uint32_t SORT_THREADS = 1024;
 
 template <class S>
 __global__ void __launch_bounds__(SORT_THREADS) k_hist_lds(const uint32_t* __restrict__ scalars, size_t n, int mont, int skip_ones, int sgn, int c, int K,
-                                                           uint32_t nbw, uint32_t nb, uint32_t* __restrict__ block_hist /* [SORT_BLOCKS][nb] */) {
+                                                           uint32_t nbw, uint32_t nb, uint32_t* __restrict__ block_hist /* [SORT_BLOCKS][nb] */, MsmRowStrides rs) {
   extern __shared__ uint32_t lds_cnt[];
+  scalars += blockIdx.y * rs.scalars; block_hist += blockIdx.y * rs.block_hist;      // (the row of a group: msm_launch_rows)
   for (uint32_t g = threadIdx.x; g < nb; g += SORT_THREADS) lds_cnt[g] = 0;
   __syncthreads();
   const size_t chunk = (n + gridDim.x - 1) / gridDim.x;
@@ -256,8 +258,12 @@ __global__ void __launch_bounds__(SORT_THREADS) k_hist_lds(const uint32_t* __res
 template <int DUMMY>
 __global__ void __launch_bounds__(1024) k_prefix_scan(uint32_t* __restrict__ block_hist, uint32_t nb, uint32_t* __restrict__ counts, uint32_t nblocks,
                                                       uint32_t* __restrict__ heavy, uint32_t* __restrict__ bucket_off, uint32_t* __restrict__ sub_off,
-                                                      uint32_t* __restrict__ totals, uint32_t sub, uint32_t heavy_min, uint32_t heavy_cap) {
+                                                      uint32_t* __restrict__ totals, uint32_t sub, uint32_t heavy_min, uint32_t heavy_cap, MsmRowStrides rs) {
   __shared__ uint32_t s_last;
+  {   // the row of a group: its slices, its own ticket (totals[2]) and heavy list
+    const size_t row = blockIdx.y;
+    block_hist += row * rs.block_hist; counts += row * rs.counts; heavy += row * rs.heavy; bucket_off += row * rs.offs; sub_off += row * rs.offs; totals += row * rs.totals;
+  }
   const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g < nb) {
     uint32_t run = 0;
@@ -283,8 +289,9 @@ __global__ void __launch_bounds__(1024) k_prefix_scan(uint32_t* __restrict__ blo
 template <class S>
 __global__ void __launch_bounds__(SORT_THREADS) k_scatter_lds(const uint32_t* __restrict__ scalars, size_t n, int mont, int skip_ones, int sgn, int c, int K,
                                                               uint32_t nbw, uint32_t nb, uint32_t pt_stride, const uint32_t* __restrict__ bucket_off,
-                                                              const uint32_t* __restrict__ block_hist, uint32_t* __restrict__ sorted) {
+                                                              const uint32_t* __restrict__ block_hist, uint32_t* __restrict__ sorted, MsmRowStrides rs) {
   extern __shared__ uint32_t lds_pos[];
+  { const size_t row = blockIdx.y; scalars += row * rs.scalars; bucket_off += row * rs.offs; block_hist += row * rs.block_hist; sorted += row * rs.sorted; }
   const uint32_t* mine = block_hist + (size_t)blockIdx.x * nb;
   for (uint32_t g = threadIdx.x; g < nb; g += SORT_THREADS) lds_pos[g] = bucket_off[g] + mine[g];
   __syncthreads();
@@ -304,7 +311,8 @@ template <class F>
 __global__ void __launch_bounds__(256, 3) k_accum(const uint32_t* __restrict__ bases, const uint32_t* __restrict__ sorted,
                                                const uint32_t* __restrict__ bucket_off, const uint32_t* __restrict__ sub_off,
                                                uint32_t nb, const uint32_t* __restrict__ totals,
-                                               uint32_t* __restrict__ partial, uint32_t sub) {
+                                               uint32_t* __restrict__ partial, uint32_t sub, MsmRowStrides rs) {
+  { const size_t row = blockIdx.y; sorted += row * rs.sorted; bucket_off += row * rs.offs; sub_off += row * rs.offs; totals += row * rs.totals; partial += row * rs.partial; }
   const uint32_t total = totals[0];
   uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= total) return;
@@ -360,9 +368,7 @@ __global__ void __launch_bounds__(256) k_ones_partial(const uint32_t* __restrict
 // at a time, queues the indices of the units in LDS (ballot + prefix count) and adds 64 queued bases at a time, one per lane; which lane
 // adds which base is irrelevant, everything is summed.  The queue is the wave's own: LDS operations of one wave execute in order.
 template <class S, class F>
-__global__ void __launch_bounds__(256) k_ones_dense(const uint32_t* __restrict__ scalars, const uint32_t* __restrict__ bases, size_t n, int mont,
-                                                    uint32_t* __restrict__ out /* ONES_THREADS XYZZ */) {
-  __shared__ uint32_t queue[4][128];
+__device__ __forceinline__ XYZZ<F> ones_dense_sum(const uint32_t* __restrict__ scalars, const uint32_t* __restrict__ bases, size_t n, int mont, uint32_t (*queue)[128]) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
   const size_t wave = t >> 6, nwaves = ONES_THREADS / 64;
   volatile uint32_t* q = queue[wv];
@@ -384,7 +390,35 @@ __global__ void __launch_bounds__(256) k_ones_dense(const uint32_t* __restrict__
     }
   }
   if (lane < cnt) { Affine<F> pt = load_affine<F>(bases, q[lane]); add_mixed(acc, pt); }
-  store_xyzz(out, t, acc);
+  return acc;
+}
+template <class S, class F>
+__global__ void __launch_bounds__(256) k_ones_dense(const uint32_t* __restrict__ scalars, const uint32_t* __restrict__ bases, size_t n, int mont,
+                                                    uint32_t* __restrict__ out /* ONES_THREADS XYZZ */) {
+  __shared__ uint32_t queue[4][128];
+  const XYZZ<F> acc = ones_dense_sum<S, F>(scalars, bases, n, mont, queue);
+  store_xyzz(out, blockIdx.x * blockDim.x + threadIdx.x, acc);
+}
+// Several unit sums in ONE launch (a row group's witness slices and S_1 prefixes): descriptor blockIdx.y, the same ONES_THREADS threads per sum, and every
+// workgroup folds its 256 partial sums in LDS before it stores — ONES_THREADS / 256 = 64 points per sum, which ONE k_tree_rows workgroup per sum finishes.
+template <class S, class F>
+__global__ void __launch_bounds__(256) k_ones_dense_rows(OnesDescs ds, int mont, uint32_t* __restrict__ lvl /* gridDim.y x gridDim.x XYZZ */) {
+  __shared__ uint32_t queue[4][128];
+  __shared__ XYZZ<F> sh[256];
+  const OnesDesc& d = ds.d[blockIdx.y];
+  sh[threadIdx.x] = ones_dense_sum<S, F>(d.scalars, d.bases, d.n, mont, queue);
+  __syncthreads();
+  quad_tree256<F>(sh);
+  if (threadIdx.x == 0) store_xyzz(lvl, (size_t)blockIdx.y * gridDim.x + blockIdx.x, sh[0]);
+}
+template <class F>
+__global__ void __launch_bounds__(256) k_tree_rows(const uint32_t* __restrict__ lvl, uint32_t m /* <= 256 points per sum */, OnesDescs ds) {
+  __shared__ XYZZ<F> sh[256];
+  const uint32_t t = threadIdx.x;
+  sh[t] = t < m ? load_xyzz<F>(lvl, (size_t)blockIdx.x * m + t) : XYZZ<F>::identity();
+  __syncthreads();
+  quad_tree256<F>(sh);
+  if (t == 0) store_xyzz(ds.d[blockIdx.x].out, 0, sh[0]);
 }
 // in: m points, out: ceil(m/256) points (one LDS tree per workgroup)
 template <class F>
@@ -415,10 +449,11 @@ template <class F>
 __global__ void __launch_bounds__(256) k_combine(uint32_t* __restrict__ partial, const uint32_t* __restrict__ sub_off, uint32_t nb, uint32_t nbn,
                                                  const uint32_t* __restrict__ heavy, uint32_t heavy_cap, uint32_t* scratch /* (written and, by the last part, read: no restrict) */,
                                                  uint32_t lane_bits /* log2 of the lanes per ordinary bucket: 0..4 */, uint32_t heavy_min,
-                                                 uint32_t* __restrict__ heavy_done /* one ticket per split bucket */) {
+                                                 uint32_t* __restrict__ heavy_done /* one ticket per split bucket */, MsmRowStrides rs) {
   __shared__ XYZZ<F> sh[256];
   __shared__ uint32_t s_last;
   const uint32_t t = threadIdx.x;
+  { const size_t row = blockIdx.y; partial += row * rs.partial; sub_off += row * rs.offs; heavy += row * rs.heavy; scratch += row * rs.heavy_scratch; heavy_done += row * rs.heavy_done; }
   if (blockIdx.x < nbn) {
     // The lanes of a bucket are idle for most of an LDS tree (8, 4, 2, 1 of 16 active), and an addition costs the wave the same
     // whether one lane or all of them take part: the host picks few lanes per bucket (about a third of the mean number of
@@ -495,8 +530,13 @@ __global__ void __launch_bounds__(256) k_combine(uint32_t* __restrict__ partial,
 template <class F>
 __global__ void __launch_bounds__(256) k_reduce(const uint32_t* __restrict__ partial, const uint32_t* __restrict__ counts,
                                                 const uint32_t* __restrict__ sub_off, uint32_t nbw,
-                                                uint32_t* __restrict__ window_sums, uint32_t* __restrict__ plain_sums = nullptr) {
+                                                uint32_t* __restrict__ window_sums, uint32_t* __restrict__ plain_sums, MsmRowStrides rs) {
   __shared__ XYZZ<F> sh[256];
+  {
+    const size_t row = blockIdx.y;
+    partial += row * rs.partial; counts += row * rs.counts; sub_off += row * rs.offs; window_sums += row * rs.out;
+    if (plain_sums) plain_sums += row * rs.out;
+  }
   const uint32_t w = blockIdx.x, t = threadIdx.x, T = blockDim.x;
   const uint32_t ch = nbw / T;
   const uint32_t lo = t * ch;
@@ -952,13 +992,18 @@ hipError_t build_tables(hipStream_t stream, const uint32_t* d_bases, size_t n, i
 // Enqueue the whole pipeline on `stream` and the copy of the K window sums into `pinned_dst` (host-pinned,
 // K * XYZZ_WORDS words).  Does not synchronise: the caller waits on the stream (or an event recorded after this call)
 // and then calls msm_finish.  `ws` must not be used by another stream concurrently.
+// The rows of a group (msm_launch_rows; rg == nullptr: msm_launch, one vector): how many, where row r's scalars and sums lie, what the workspace is sized for,
+// the caller's further unit sums.  A shape the grouped chain does not cover returns hipErrorNotSupported BEFORE anything is launched or reserved.
+struct MsmRowGroup { uint32_t G; size_t scalar_row_stride /* scalars */, pinned_row_stride /* bytes */; const OnesDesc* extra; uint32_t n_extra; uint32_t max_rows; size_t* row_bytes_out /* only report a row's device bytes */; };
 template <class C>
-hipError_t msm_launch(hipStream_t stream, MsmWorkspace& ws, const uint32_t* d_bases, const uint32_t* d_scalars, size_t n,
-                      int scalars_mont, int c_override, void* pinned_dst, MsmPlan* plan_out, hipEvent_t* ev, int split_ones,
-                      const BaseTables* tb) {
+static hipError_t msm_launch_impl(hipStream_t stream, MsmWorkspace& ws, const uint32_t* d_bases, const uint32_t* d_scalars, size_t n,
+                                  int scalars_mont, int c_override, void* pinned_dst, MsmPlan* plan_out, hipEvent_t* ev, int split_ones,
+                                  const BaseTables* tb, const MsmRowGroup* rg) {
   typedef typename C::Coord F;
   typedef typename C::Scalar S;
   if (n == 0 || n >= (1u << 31)) return hipErrorInvalidValue;
+  const uint32_t G = rg ? rg->G : 1u;
+  if (rg && !rg->row_bytes_out && (G == 0 || G > MSM_ROWS_MAX || rg->n_extra > MSM_ROWS_MAX || (split_ones == 0 && rg->n_extra))) return hipErrorInvalidValue;
   const int sgn = msm_tuning().signed_scalars;
   // The window sums go straight into the caller's pinned buffer (host memory the device can write): the copy that used to follow —
   // a launch and a dependent hop between the last kernel and the host's wake-up — is gone.
@@ -973,6 +1018,7 @@ hipError_t msm_launch(hipStream_t stream, MsmWorkspace& ws, const uint32_t* d_ba
   const bool own = tabled && tb->own;
   if (small_tb && (n > MSM_SMALL_MAX || tb->K != (S::Params::BITS + SMALL_C) / SMALL_C)) return hipErrorInvalidValue;
   if (!no_small && !tabled && c_override <= 0 && n <= MSM_SMALL_MAX) {      // fused single-launch path
+    if (rg) return hipErrorNotSupported;
     MsmPlan ps; ps.c = SMALL_C; ps.K = (S::Params::BITS + SMALL_C) / SMALL_C; ps.nbw = SMALL_NBW; ps.nb = SMALL_NBW * (uint32_t)ps.K; ps.split_ones = 0; ps.tabled = small_tb ? 2 : 0;
     *plan_out = ps;
     VZ_HIP_CHECK(ws.reserve_small());
@@ -1018,6 +1064,8 @@ hipError_t msm_launch(hipStream_t stream, MsmWorkspace& ws, const uint32_t* d_ba
   while (Gp > 1 && (Pl + 2) * Gp > 256) Gp >>= 1;
   const bool planes = tabled && !own && !no_planes && pl.nbw >= 1024 && (1u << Pl) == pl.nbw && (Pl + 2) * Gp <= 256 && (int)Pl + 2 + 1 <= MSM_MAX_WINDOWS;
   if (planes) pl.tabled = 4;
+  const bool lds_sort = (size_t)pl.nb * 4 <= 144 * 1024;      // all buckets' counters fit in one workgroup's LDS at the default window (24 x 1024 x 4 B = 96 KiB): contention-free sort
+  if (rg && (planes || own || !lds_sort)) return hipErrorNotSupported;
   // (ONE assignment, every field final: the plan object is often shared — the producer's issuer thread launches row r + k while the folding thread
   //  finishes row r with the same plan, msm_finish — and a launch must never be seen half-described)
   *plan_out = pl;
@@ -1032,13 +1080,19 @@ hipError_t msm_launch(hipStream_t stream, MsmWorkspace& ws, const uint32_t* d_ba
   const int dsub = tb && tb->sub_hint > 0 ? tb->sub_hint : msm_tuning().dense_sub;      // (a caller that knows its vector is sparse — ivc.hip's boolean-row form — asks for shorter pieces)
   const uint32_t sub = n < (1u << 15) ? 8u : split_ones ? (uint32_t)(wsub > 0 ? wsub : n < (1u << 19) ? 8 : MSM_SUB) : (uint32_t)(dsub >= 2 && dsub <= (int)MSM_SUB ? dsub : MSM_SUB);   // MSM_SUB for everything large
   const size_t max_subs = entries / sub + pl.nb + 1;
-  VZ_HIP_CHECK(ws.reserve(pl.nb, entries, max_subs));
+  if (rg && rg->row_bytes_out) { *rg->row_bytes_out = MsmWorkspace::row_bytes(pl.nb, entries, max_subs, (size_t)SORT_BLOCKS * pl.nb); return hipSuccess; }
+  VZ_HIP_CHECK(ws.reserve(pl.nb, entries, max_subs, rg ? std::max<size_t>(G, rg->max_rows) : 1));
+  // row slices: strides of this call's sizes (the tickets' arrays — totals, heavy_done — keep fixed strides, so every ticket stays where it was zeroed)
+  MsmRowStrides rs;
+  if (G > 1) {
+    rs.scalars = 8 * rg->scalar_row_stride; rs.block_hist = (size_t)SORT_BLOCKS * pl.nb; rs.sorted = entries; rs.partial = (size_t)XYZZ_WORDS * max_subs;
+    rs.heavy_scratch = MsmWorkspace::HEAVY_SCRATCH_WORDS; rs.out = rg->pinned_row_stride / 4;
+    rs.counts = pl.nb; rs.offs = pl.nb + 1; rs.totals = MsmWorkspace::TOTALS_WORDS; rs.heavy = MsmWorkspace::HEAVY_CAP + 1; rs.heavy_done = MsmWorkspace::HEAVY_DONE_WORDS;
+  }
   const int TB = 256;
 #define VZ_EV(i) do { if (ev) VZ_HIP_CHECK(hipEventRecord(ev[i], stream)); } while (0)
   VZ_EV(0);
   const unsigned gs = (unsigned)std::min<size_t>((n + TB - 1) / TB, 256 * 16);
-  // all buckets' counters fit in one workgroup's LDS at the default window (24 x 1024 x 4 B = 96 KiB): contention-free sort
-  const bool lds_sort = (size_t)pl.nb * 4 <= 144 * 1024;
   if (!lds_sort) {      // (the LDS sort writes every counter itself and needs no cursors; each fill is a launch of its own)
     VZ_HIP_CHECK(hipMemsetAsync(ws.counts, 0, 4 * (size_t)pl.nb, stream));
     VZ_HIP_CHECK(hipMemsetAsync(ws.cursor, 0, 4 * (size_t)pl.nb, stream));
@@ -1065,7 +1119,7 @@ hipError_t msm_launch(hipStream_t stream, MsmWorkspace& ws, const uint32_t* d_ba
         attr_devices |= 1ull << (dev & 63);
       }
     }
-    hipLaunchKernelGGL(k_hist_lds<S>, dim3(sort_blocks), dim3(SORT_THREADS), pl.nb * 4, stream, d_scalars, n, scalars_mont, split_ones, sgn, pl.c, pl.K, bstride, pl.nb, ws.block_hist);
+    hipLaunchKernelGGL(k_hist_lds<S>, dim3(sort_blocks, G), dim3(SORT_THREADS), pl.nb * 4, stream, d_scalars, n, scalars_mont, split_ones, sgn, pl.c, pl.K, bstride, pl.nb, ws.block_hist, rs);
   } else {
     hipLaunchKernelGGL(k_hist<S>, dim3(gs), dim3(TB), 0, stream, d_scalars, n, scalars_mont, split_ones, sgn, pl.c, pl.K, bstride, ws.counts);
   }
@@ -1080,14 +1134,14 @@ hipError_t msm_launch(hipStream_t stream, MsmWorkspace& ws, const uint32_t* d_ba
   const uint32_t lane_bits = lane_bits_env >= 0 ? (uint32_t)lane_bits_env : mean_parts > 96 ? 4u : mean_parts > 48 ? 3u : mean_parts > 24 ? 2u : 1u;
   const uint32_t heavy_min = 16u << lane_bits;
   if (lds_sort)      // per-workgroup histograms -> prefixes and totals, and (last workgroup) the scan: one launch
-    hipLaunchKernelGGL(k_prefix_scan<0>, dim3((pl.nb + 1023) / 1024), dim3(1024), 0, stream, ws.block_hist, pl.nb, ws.counts, sort_blocks, ws.heavy, ws.bucket_off, ws.sub_off,
-                       ws.totals, sub, heavy_min, MsmWorkspace::HEAVY_CAP);
+    hipLaunchKernelGGL(k_prefix_scan<0>, dim3((pl.nb + 1023) / 1024, G), dim3(1024), 0, stream, ws.block_hist, pl.nb, ws.counts, sort_blocks, ws.heavy, ws.bucket_off, ws.sub_off,
+                       ws.totals, sub, heavy_min, MsmWorkspace::HEAVY_CAP, rs);
   else
     hipLaunchKernelGGL(k_scan<MSM_SUB>, dim3(1), dim3(1024), 0, stream, ws.counts, pl.nb, ws.bucket_off, ws.sub_off, ws.totals, sub, ws.heavy, heavy_min, MsmWorkspace::HEAVY_CAP);
   VZ_EV(2);
   if (lds_sort)
-    hipLaunchKernelGGL(k_scatter_lds<S>, dim3(sort_blocks), dim3(SORT_THREADS), pl.nb * 4, stream, d_scalars, n, scalars_mont, split_ones, sgn, pl.c, pl.K, bstride, pl.nb,
-                       pstride, ws.bucket_off, ws.block_hist, ws.sorted);
+    hipLaunchKernelGGL(k_scatter_lds<S>, dim3(sort_blocks, G), dim3(SORT_THREADS), pl.nb * 4, stream, d_scalars, n, scalars_mont, split_ones, sgn, pl.c, pl.K, bstride, pl.nb,
+                       pstride, ws.bucket_off, ws.block_hist, ws.sorted, rs);
   else
     hipLaunchKernelGGL(k_scatter<S>, dim3(gs), dim3(TB), 0, stream, d_scalars, n, scalars_mont, split_ones, sgn, pl.c, pl.K, bstride, pstride,
                        ws.bucket_off, ws.cursor, ws.sorted);
@@ -1099,12 +1153,12 @@ hipError_t msm_launch(hipStream_t stream, MsmWorkspace& ws, const uint32_t* d_ba
   //  worse at one, in the 20-row window, over 256 rows and on one chain: profiles/r05_segments_queues_sweep.txt)
   const size_t accum_lds = (size_t)msm_tuning().accum_lds_kb * 1024;
   if (accum_lds > 65536) { static const hipError_t once = hipFuncSetAttribute((const void*)k_accum<F>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); (void)once; }
-  hipLaunchKernelGGL(k_accum<F>, dim3(ga), dim3(TB), accum_lds, stream, d_bases, ws.sorted, ws.bucket_off, ws.sub_off, pl.nb,
-                     ws.totals, partial, sub);
+  hipLaunchKernelGGL(k_accum<F>, dim3(ga, G), dim3(TB), accum_lds, stream, d_bases, ws.sorted, ws.bucket_off, ws.sub_off, pl.nb,
+                     ws.totals, partial, sub, rs);
   VZ_EV(4);
   const unsigned per_wg = 256u >> lane_bits, nbn = (pl.nb + per_wg - 1) / per_wg;
-  hipLaunchKernelGGL(k_combine<F>, dim3(nbn + COMBINE_HEAVY_BLOCKS + COMBINE_SPLIT_BLOCKS), dim3(256), 0, stream, partial, ws.sub_off, pl.nb, nbn,
-                     (const uint32_t*)ws.heavy, MsmWorkspace::HEAVY_CAP, ws.heavy_scratch, lane_bits, heavy_min, ws.heavy_done);
+  hipLaunchKernelGGL(k_combine<F>, dim3(nbn + COMBINE_HEAVY_BLOCKS + COMBINE_SPLIT_BLOCKS, G), dim3(256), 0, stream, partial, ws.sub_off, pl.nb, nbn,
+                     (const uint32_t*)ws.heavy, MsmWorkspace::HEAVY_CAP, ws.heavy_scratch, lane_bits, heavy_min, ws.heavy_done, rs);
   VZ_EV(5);      // (stage 2 of the very heavy buckets: the last of a bucket's workgroups, inside k_combine)
   const unsigned T = pl.nbw < 256 ? pl.nbw : 256;
   uint32_t* wsum = direct ? reinterpret_cast<uint32_t*>(pinned_dst) : reinterpret_cast<uint32_t*>(ws.window_sums);
@@ -1115,12 +1169,17 @@ hipError_t msm_launch(hipStream_t stream, MsmWorkspace& ws, const uint32_t* d_ba
     hipLaunchKernelGGL(k_reduce_planes<F>, dim3((Pl + 2) * Gp), dim3(256), 0, stream, (const uint32_t*)partial, (const uint32_t*)ws.counts, (const uint32_t*)ws.sub_off, pl.nbw, Pl, Gp,
                        pl.nbw / (512u * Gp), ws.plane_scratch, ws.totals + 3, wsum);
   } else if (tabled && !own) {
-    hipLaunchKernelGGL(k_reduce<F>, dim3(V), dim3(vw < 256 ? vw : 256), 0, stream, (const uint32_t*)partial, (const uint32_t*)ws.counts, (const uint32_t*)ws.sub_off, vw, wsum, wsum + (size_t)XYZZ_WORDS * V);
+    hipLaunchKernelGGL(k_reduce<F>, dim3(V, G), dim3(vw < 256 ? vw : 256), 0, stream, (const uint32_t*)partial, (const uint32_t*)ws.counts, (const uint32_t*)ws.sub_off, vw, wsum, wsum + (size_t)XYZZ_WORDS * V, rs);
   } else
-    hipLaunchKernelGGL(k_reduce<F>, dim3(pl.K), dim3(T), 0, stream, (const uint32_t*)partial, (const uint32_t*)ws.counts, (const uint32_t*)ws.sub_off, pl.nbw, wsum);
+    hipLaunchKernelGGL(k_reduce<F>, dim3(pl.K, G), dim3(T), 0, stream, (const uint32_t*)partial, (const uint32_t*)ws.counts, (const uint32_t*)ws.sub_off, pl.nbw, wsum, (uint32_t*)nullptr, rs);
   VZ_EV(6);
 #undef VZ_EV
-  if (split_ones) {   // sum of the bases with unit scalar -> window_sums[K]
+  if (split_ones && rg) {   // a group's unit sums -> each row's window_sums[K], and the caller's own, in two launches
+    OnesDesc ds[2 * MSM_ROWS_MAX];
+    for (uint32_t r = 0; r < G; r++) ds[r] = OnesDesc{d_scalars + 8 * r * rg->scalar_row_stride, d_bases, wsum + r * (rg->pinned_row_stride / 4) + (size_t)XYZZ_WORDS * kout, n};
+    for (uint32_t e = 0; e < rg->n_extra; e++) ds[G + e] = rg->extra[e];
+    VZ_HIP_CHECK(ones_launch_rows<C>(stream, ws, ds, G + rg->n_extra, scalars_mont));
+  } else if (split_ones) {   // sum of the bases with unit scalar -> window_sums[K]
     uint32_t* lvl0 = reinterpret_cast<uint32_t*>(ws.ones_partial);
     if (msm_tuning().ones_dense) hipLaunchKernelGGL((k_ones_dense<S, F>), dim3(ONES_THREADS / 256), dim3(256), 0, stream, d_scalars, d_bases, n, scalars_mont, lvl0);
     else hipLaunchKernelGGL((k_ones_partial<S, F>), dim3(ONES_THREADS / 256), dim3(256), 0, stream, d_scalars, d_bases, n, scalars_mont, lvl0);
@@ -1131,6 +1190,34 @@ hipError_t msm_launch(hipStream_t stream, MsmWorkspace& ws, const uint32_t* d_ba
   VZ_HIP_CHECK(hipGetLastError());
   if (!direct) VZ_HIP_CHECK(hipMemcpyAsync(pinned_dst, wsum, 4 * (size_t)XYZZ_WORDS * (kout + (split_ones ? 1 : 0)), hipMemcpyDeviceToHost, stream));
   return hipSuccess;
+}
+
+template <class C>
+hipError_t msm_launch(hipStream_t stream, MsmWorkspace& ws, const uint32_t* d_bases, const uint32_t* d_scalars, size_t n,
+                      int scalars_mont, int c_override, void* pinned_dst, MsmPlan* plan_out, hipEvent_t* ev, int split_ones,
+                      const BaseTables* tb) {
+  return msm_launch_impl<C>(stream, ws, d_bases, d_scalars, n, scalars_mont, c_override, pinned_dst, plan_out, ev, split_ones, tb, nullptr);
+}
+template <class C>
+hipError_t msm_launch_rows(hipStream_t stream, MsmWorkspace& ws, const uint32_t* d_bases, const uint32_t* d_scalars, size_t n, size_t scalar_row_stride, uint32_t G,
+                           int scalars_mont, void* pinned_dst, size_t pinned_row_stride, MsmPlan* plan_out, int split_ones, const BaseTables* tb,
+                           const OnesDesc* extra, uint32_t n_extra, uint32_t max_rows) {
+  if (G > 1 && (scalar_row_stride < n || (pinned_row_stride & 15))) return hipErrorInvalidValue;
+  const MsmRowGroup rg{G, scalar_row_stride, pinned_row_stride, extra, n_extra, max_rows, nullptr};
+  const hipError_t e = msm_launch_impl<C>(stream, ws, d_bases, d_scalars, n, scalars_mont, 0, pinned_dst, plan_out, nullptr, split_ones, tb, &rg);
+  if (e != hipErrorNotSupported) return e;
+  // a shape the grouped chain does not cover: row after row
+  for (uint32_t r = 0; r < G; r++)
+    VZ_HIP_CHECK(msm_launch<C>(stream, ws, d_bases, d_scalars + 8 * r * scalar_row_stride, n, scalars_mont, 0, (char*)pinned_dst + r * pinned_row_stride, plan_out, nullptr, split_ones, tb));
+  if (n_extra) VZ_HIP_CHECK(ones_launch_rows<C>(stream, ws, extra, n_extra, scalars_mont));
+  return hipSuccess;
+}
+template <class C>
+size_t msm_rows_row_bytes(size_t n, int split_ones, const BaseTables* tb) {
+  size_t bytes = 0;
+  MsmWorkspace none; MsmPlan pl;
+  const MsmRowGroup rg{1, n, 0, nullptr, 0, 0, &bytes};
+  return msm_launch_impl<C>(nullptr, none, tb ? tb->d : nullptr, nullptr, n, 1, 0, nullptr, &pl, nullptr, split_ones, tb, &rg) == hipSuccess ? bytes : 0;
 }
 
 // Host tail: Horner over the K window sums (converted to the standard form, whose host multiply is the fast 4x64 path)
@@ -1191,6 +1278,22 @@ hipError_t ones_launch(hipStream_t stream, MsmWorkspace& ws, const uint32_t* d_b
   hipLaunchKernelGGL(k_tree256<F>, dim3(1), dim3(256), 0, stream, lvl1, ONES_THREADS / 256, top);
   VZ_HIP_CHECK(hipGetLastError());
   return hipMemcpyAsync(pinned_dst, top, 4 * (size_t)XYZZ_WORDS, hipMemcpyDeviceToHost, stream);
+}
+template <class C>
+hipError_t ones_launch_rows(hipStream_t stream, MsmWorkspace& ws, const OnesDesc* descs, uint32_t count, int scalars_mont) {
+  typedef typename C::Coord F;
+  typedef typename C::Scalar S;
+  if (!count) return hipSuccess;
+  if (count > 2 * MSM_ROWS_MAX) return hipErrorInvalidValue;
+  if (!ws.ones_partial) VZ_HIP_CHECK(hipMalloc(&ws.ones_partial, 4 * (size_t)XYZZ_WORDS * (16384 + 64 + 512)));      // (as ones_launch; 2·MSM_ROWS_MAX x 64 points are used here)
+  static_assert(2 * MSM_ROWS_MAX * (ONES_THREADS / 256) <= 16384, "the groups' partial sums fit ones_partial");
+  OnesDescs ds;
+  for (uint32_t i = 0; i < count; i++) ds.d[i] = descs[i];
+  for (uint32_t i = count; i < 2 * MSM_ROWS_MAX; i++) ds.d[i] = OnesDesc{nullptr, nullptr, nullptr, 0};
+  uint32_t* lvl = reinterpret_cast<uint32_t*>(ws.ones_partial);
+  hipLaunchKernelGGL((k_ones_dense_rows<S, F>), dim3(ONES_THREADS / 256, count), dim3(256), 0, stream, ds, scalars_mont, lvl);
+  hipLaunchKernelGGL(k_tree_rows<F>, dim3(count), dim3(256), 0, stream, (const uint32_t*)lvl, ONES_THREADS / 256, ds);
+  return hipGetLastError();
 }
 template <class C>
 XYZZ<typename C::Base> ones_finish(const void* pinned) {

@@ -19,6 +19,7 @@ HostPool& vz_shared_pool() {
 }
 
 std::atomic<long>& vz_head_rows_override() { static std::atomic<long> v{-1}; return v; }
+std::atomic<long>& vz_rows_group_override() { static std::atomic<long> v{-1}; return v; }
 
 extern "C" {
 
@@ -214,6 +215,7 @@ extern "C" {
 // Rows of a short fold call whose Poseidon chains are evaluated on the HOST (the head batch, prover_internal.hpp): rows >= 0 pins the number for
 // every later call of this process (0 = every row's witness entirely on the GPU), -1 restores the library's policy.  Returns the previous setting.
 long vimz_set_head_rows(long rows) { return vz_head_rows_override().exchange(rows < 0 ? -1 : rows); }
+long vimz_set_rows_group(long rows) { return vz_rows_group_override().exchange(rows < 0 ? -1 : rows); }
 
 int vimz_prover_reset(vimz_prover* p, const uint64_t* z0) {
   if (!p || !z0) return VIMZ_ERR_INVALID;

@@ -485,9 +485,23 @@ static void plan_batches(FoldJob& J, size_t first, size_t n, size_t B) {
 
 template <int DUMMY>
 __global__ void k_row_flag(uint32_t* flag, uint32_t v) { __hip_atomic_store(flag, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
+template <int DUMMY>
+__global__ void k_row_flags(uint32_t* flag, uint32_t v, uint32_t n) { if (threadIdx.x < n) __hip_atomic_store(flag + threadIdx.x, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
 static inline hipError_t mark_row(hipStream_t st, vimz_prover::BatchBuf& bb, size_t idx) {
   hipLaunchKernelGGL(k_row_flag<0>, dim3(1), dim3(1), 0, st, bb.row_flag + idx, bb.gen);
   return hipGetLastError();
+}
+// Row groups of the producer (fold_issue): the most rows whose witness commitments and S_1 sums go out as ONE chain of launches.  0 / 1: row after row, as
+// before round 8 — the same binary, for A/B runs and the tests that require the identical proof either way.  vimz_set_rows_group pins it for the process,
+// VIMZ_TUNE=rows_group=N for a run.  The default is 4: groups of 2 / 4 / 8 / 16 rows measured the same within the run-to-run spread (256 rows: 1 395 / 1 423 / 1 410 /
+// 1 367 steps/s against the parent's 1 296; profiles/r08_rows_group_ab.txt), and every row of a group is 143 MB of workspace at contrast HD.
+std::atomic<long>& vz_rows_group_override();      // vimz_set_rows_group: -1 = VIMZ_TUNE's value, or the default
+constexpr size_t ROWS_GROUP_DEFAULT = 4, ROWS_GROUP_BYTES_MAX = (size_t)2 << 30;      // (a workspace's row slices stay below 2 GiB)
+static size_t rows_group_wanted() {
+  static const long env = [] { const char* e = getenv("VIMZ_TUNE"); const char* q = e ? strstr(e, "rows_group=") : nullptr; return q ? atol(q + 11) : -1L; }();
+  const long ov = vz_rows_group_override().load(std::memory_order_relaxed);
+  const long v = ov >= 0 ? ov : env >= 0 ? env : (long)ROWS_GROUP_DEFAULT;
+  return (size_t)std::min<long>(v, (long)MSM_ROWS_MAX);
 }
 // The fold thread's wait for row idx of a batch that has been issued (the word is written in stream order behind the row's results, which
 // went to pinned memory too), and the ONLY way the fold's streams depend on the producer's: what they launch for a row is launched after
@@ -1015,6 +1029,38 @@ static int fold_issue(vimz_prover* p, const FoldJob& J, size_t k) {
   // between the producer's stream and the head batch's (idle after the first rows of a call), each with its own MSM workspace.
   const bool two = p->ivc && p->sH && p->sH != sb;
   if (two) P_TRY(hipStreamWaitEvent(p->sH, bb.wit_done, 0));
+  // ROW GROUPS.  The whole batch's witnesses exist before the first commitment is issued, and a row's chain is dependent launches of grids that fill 6-30 % of
+  // the GPU: up to rows_group_wanted() rows go out as ONE chain (msm_launch_rows: the row in blockIdx.y; the group's 2G unit sums in two launches), the groups
+  // alternating between the two streams and workspaces as the rows did.  The first GPU-produced batch of a call ramps up — 1, 1, 2, 4, ... — so that its first
+  // fold starts no later than with one chain per row.  The lookahead schedule and circuits on the fused small path keep the per-row issue below.
+  const BaseTables* tbW = p->ck->tables ? &J.tbl : nullptr;
+  size_t gmax = p->want_d ? 0 : std::min(rows_group_wanted(), p->max_batch);
+  if (gmax > 1) {
+    const size_t row_bytes = msm_rows_row_bytes<BnG1>(sw - p->c0, 1, tbW);
+    gmax = row_bytes ? std::min(gmax, std::max<size_t>(1, ROWS_GROUP_BYTES_MAX / row_bytes)) : 0;
+  }
+  if (gmax > 1) {
+    const bool ramp = k == (J.head ? 1u : 0u);
+    size_t gi = 0;
+    for (size_t r = 0; r < rows; gi++) {
+      const size_t g = std::min(std::min(gmax, rows - r), ramp ? (gi == 0 ? (size_t)1 : (size_t)1 << std::min<size_t>(gi - 1, 8)) : gmax);
+      hipStream_t st = two && (gi & 1) ? p->sH : sb;
+      MsmWorkspace& ws = two && (gi & 1) ? p->wsH : p->wsB;
+      OnesDesc s1[MSM_ROWS_MAX];
+      for (size_t i = r; i < r + g; i++) {
+        launch_spmv(p, st, bb.Z + 8 * i * nw, bb.az + 8 * i * nc, bb.bz + 8 * i * nc, bb.cz + 8 * i * nc, 1);
+        if (p->ivc) P_TRY(hipEventRecord(bb.ev_p[i], st));
+        s1[i - r] = OnesDesc{bb.az + 8 * i * nc, p->ck->d, reinterpret_cast<uint32_t*>((char*)bb.pin + i * FoldJob::pin_stride + vimz_prover::S1_SLOT), p->n_bool};
+      }
+      P_TRY(msm_launch_rows<BnG1>(st, ws, p->ck->d, bb.Z + 8 * (r * nw + (size_t)p->c0), sw - p->c0, nw, (uint32_t)g, 1, (char*)bb.pin + r * FoldJob::pin_stride, FoldJob::pin_stride,
+                                  &p->planB, 1, tbW, s1, p->want_s1 ? (uint32_t)g : 0u, (uint32_t)gmax));
+      hipLaunchKernelGGL(k_row_flags<0>, dim3(1), dim3(64), 0, st, bb.row_flag + r, bb.gen, (uint32_t)g);
+      P_TRY(hipGetLastError());
+      for (size_t i = r; i < r + g; i++) P_TRY(hipEventRecord(bb.ev[i], st));
+      r += g;
+    }
+    return VIMZ_OK;
+  }
   for (size_t r = 0; r < rows; r++) {
     const uint32_t* Zi = bb.Z + 8 * r * nw;
     hipStream_t st = two && (r & 1) ? p->sH : sb;

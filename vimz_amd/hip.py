@@ -882,6 +882,14 @@ def set_head_rows(rows):
     return int(lib.vimz_set_head_rows(int(rows)))
 
 
+def set_rows_group(rows):
+    """vimz_set_rows_group: the most rows of a batch whose witness commitments the producer issues as one chain of launches (0 / 1: per row; -1: the default)."""
+    lib = L.lib()
+    lib.vimz_set_rows_group.argtypes = [C.c_long]
+    lib.vimz_set_rows_group.restype = C.c_long
+    return int(lib.vimz_set_rows_group(int(rows)))
+
+
 class Decider:
     """vimz_decider: `Decider::preprocess` / `prove` / `verify` of the Sonobe backend (vimz/src/sonobe_backend/mod.rs:72-80) — the 25 calldata words of
     contracts/*Verifier.sol and their local verification.  prover: a CycleFoldIVC (shapes, keys, context; keep it open); kzg_vk: [tau]G2 of the SRS
