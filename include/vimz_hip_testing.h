@@ -70,6 +70,17 @@ int vimz_test_cross_term_masked(vimz_ctx* ctx, size_t n, const vimz_vec* az1, co
  * producer's S_1 sums do (s1_xy, calls·G points) and is computed again by one ones_launch per row (s1_ref_xy, G points). */
 int vimz_test_msm_rows(vimz_ctx* ctx, const vimz_bases* bases, const uint64_t* scalars, size_t n, size_t row_stride, size_t G, int form, int use_tables,
                        size_t n_ones, int calls, uint64_t* out_xy, uint64_t* s1_xy, uint64_t* s1_ref_xy);
+/* The decider's kernels (vimz_amd/csrc/groth16.hip) on a caller's shapes, through the functions the set-up and the prover call (tests/test_gpu_g16_kernels.py).
+ * The domain of n = 2^logn points, logn in 1..26, with the constants and twiddle tables a key holds: a, b, c and out are HOST arrays of n scalars of 4 words
+ * (form = VIMZ_FORM_*, out in the same form).  what = 0: the forward NTT of a; 1: the inverse NTT of a, UNSCALED (n times the inverse); 2: a's evaluations
+ * over the coset 5·H (inverse, scale by 5^i / n, forward); 3: the n coefficients of h = (A·B − C) / Z for the evaluations a, b, c (b, c: only here). */
+int vimz_test_g16_domain(vimz_ctx* ctx, int logn, int what, const uint64_t* a, const uint64_t* b, const uint64_t* c, int form, uint64_t* out);
+/* s_i·G for n >= 1 canonical scalars below r as the set-up makes its key points (the host's window table, k_fixed_mul): group = 1 the generator of G1, out_xy 8
+ * words per point (x, y); group = 2 the generator of G2, 16 words per point (x.c0, x.c1, y.c0, y.c1).  Canonical; the identity as zeros. */
+int vimz_test_g16_fixed_mul(vimz_ctx* ctx, int group, const uint64_t* scalars, size_t n, uint64_t* out_xy);
+/* the proof's G2 multi-scalar multiplication on a caller's query: sum of wires[idx[i]]·P_i over n >= 1 points of G2 (canonical, 16 words each, the identity as
+ * zeros), m >= n wire values of 4 words (form = VIMZ_FORM_*) and n wire numbers below m.  out_xy: the affine sum, canonical, the identity as zeros. */
+int vimz_test_g16_g2_msm(vimz_ctx* ctx, const uint64_t* bases_xy, size_t n, const uint64_t* wires, size_t m, int form, const uint32_t* idx, uint64_t out_xy[16]);
 
 #ifdef __cplusplus
 }

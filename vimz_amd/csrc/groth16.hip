@@ -18,6 +18,9 @@
 #include "aug/decider.hpp"
 #include "pairing.hpp"
 #include "vecops_api.hpp"
+#ifdef VIMZ_TESTING
+#include "../../include/vimz_hip_testing.h"
+#endif
 
 namespace {
 
@@ -260,7 +263,63 @@ hipError_t ntt(hipStream_t s, uint32_t* d, const G16Key& K, bool inverse) {
     hipLaunchKernelGGL(k_ntt_stage, dim3((K.n / 2 + 255) / 256), dim3(256), 0, s, d, K.n, half, (const uint32_t*)(inverse ? K.tw_inv : K.tw));
   return hipGetLastError();
 }
-
+// ---- the domain H of n = 2^logn points: its constants (host), then its twiddle tables (device; the caller holds the context's lock) ------------------
+// false: Fr has no primitive root of unity of that order (logn beyond 26 is refused: the kernels index with 32 bits)
+bool domain_constants(G16Key& K, int logn) {
+  if (logn < 0 || logn > 26) return false;
+  K.logn = logn; K.n = 1u << logn;
+  K.omega = fr_root_of_unity(K.logn); K.omega_inv = Fe::pow_pm2(K.omega);
+  K.n_inv = Fe::pow_pm2(cb::f_from_u64<Fe>(K.n));
+  K.coset = cb::f_from_u64<Fe>(5); K.coset_inv = Fe::pow_pm2(K.coset);
+  K.zinv = Fe::pow_pm2(Fe::sub(fr_pow_u64(K.coset, K.n), Fe::one()));
+  const Fe chk = fr_pow_u64(K.omega, K.n / 2);
+  return K.n == 1 || Fe::add(chk, Fe::one()).is_zero();
+}
+int domain_tables(vimz_ctx* ctx, hipStream_t s, G16Key& K) {
+  P_TRY(hipMalloc((void**)&K.tw, 32 * (size_t)std::max<uint32_t>(K.n / 2, 1))); P_TRY(hipMalloc((void**)&K.tw_inv, 32 * (size_t)std::max<uint32_t>(K.n / 2, 1)));
+  Fr w, wi; memcpy(w.v, K.omega.v, 32); memcpy(wi.v, K.omega_inv.v, 32);
+  hipLaunchKernelGGL(k_pow_table, dim3((K.n / 2 + 255) / 256), dim3(256), 0, s, K.tw, (size_t)K.n / 2, w);
+  hipLaunchKernelGGL(k_pow_table, dim3((K.n / 2 + 255) / 256), dim3(256), 0, s, K.tw_inv, (size_t)K.n / 2, wi);
+  P_TRY(hipGetLastError()); P_TRY(hipStreamSynchronize(s));
+  return VIMZ_OK;
+}
+Fr as_fr(const Fe& x) { Fr r; memcpy(r.v, x.v, 32); return r; }
+// evaluations over H -> evaluations over the coset 5·H, in place
+hipError_t coset_extend(hipStream_t s, uint32_t* d, const G16Key& K) {
+  hipError_t e = ntt(s, d, K, true); if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_scale_pow, dim3((K.n + 255) / 256), dim3(256), 0, s, d, K.n, as_fr(K.n_inv), as_fr(K.coset));
+  return ntt(s, d, K, false);
+}
+// h = (a·b − c) / Z on the coset 5·H: dv[0..2] = (A·z, B·z, C·z) over H; dv[0] leaves as the n coefficients of h, dv[1] and dv[2] are spent.  Not synchronized.
+hipError_t quotient(hipStream_t s, uint32_t* const dv[3], const G16Key& K) {
+  const unsigned gb = (K.n + 255) / 256;
+  for (int q = 0; q < 3; q++) { const hipError_t e = coset_extend(s, dv[q], K); if (e != hipSuccess) return e; }
+  hipLaunchKernelGGL(k_quotient, dim3(gb), dim3(256), 0, s, dv[0], (const uint32_t*)dv[1], (const uint32_t*)dv[2], K.n, as_fr(K.zinv));
+  const hipError_t e = ntt(s, dv[0], K, true); if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_scale_pow, dim3(gb), dim3(256), 0, s, dv[0], K.n, as_fr(K.n_inv), as_fr(K.coset_inv));
+  return hipGetLastError();
+}
+// Σ_i z[idx_i]·P_i over n G2 points, bit plane by bit plane (k_g2_planes): bases, wires (Montgomery) and wire numbers on the device; canon = 8 n words of
+// device scratch for the canonical scalars; the 254 plane sums are added on the host by Horner
+int g2_msm(vimz_ctx* ctx, hipStream_t s, const G2PAff* bases, const uint32_t* wires, const uint32_t* idx, uint32_t n, uint32_t* canon, G2P* out) {
+  G2P sum = G2P::identity();
+  if (n) {
+    G2P* dpart = nullptr;
+    P_TRY(hipMalloc((void**)&dpart, sizeof(G2P) * ((size_t)G2_PLANES * G2_PLANE_THREADS + G2_PLANES)));
+    struct FreePart { G2P* p; ~FreePart() { hipFree(p); } } fp{dpart};
+    G2P* dsum = dpart + (size_t)G2_PLANES * G2_PLANE_THREADS;
+    hipLaunchKernelGGL(k_g2_canon, dim3((n + 255) / 256), dim3(256), 0, s, wires, idx, n, canon);
+    hipLaunchKernelGGL(k_g2_planes, dim3(G2_PLANE_THREADS / 256, G2_PLANES), dim3(256), 0, s, bases, (const uint32_t*)canon, n, dpart);
+    hipLaunchKernelGGL(k_g2_plane_tree, dim3(G2_PLANES), dim3(128), 0, s, (const G2P*)dpart, dsum);
+    P_TRY(hipGetLastError());
+    std::vector<G2P> planes(G2_PLANES);
+    P_TRY(hipMemcpyAsync(planes.data(), dsum, sizeof(G2P) * G2_PLANES, hipMemcpyDeviceToHost, s));
+    P_TRY(hipStreamSynchronize(s));
+    for (int j = (int)G2_PLANES - 1; j >= 0; j--) { sum = dbl(sum); add_full(sum, planes[j]); }
+  }
+  *out = sum;
+  return VIMZ_OK;
+}
 
 // (A,B,C)·z of a builder's CSR on the host threads
 template <class FF>
@@ -428,11 +487,7 @@ int decider_setup_impl(vimz_cf* v, const uint64_t kzg_vk_g2[16], const Trapdoor&
   if (K.logn > 26) return vz_fail(ctx, VIMZ_ERR_INVALID, "decider: circuit too large for the domain");
   const Fe tau = td.tau, alpha = td.alpha, beta = td.beta, gamma = td.gamma, delta = td.delta;
   const Fe gamma_inv = Fe::pow_pm2(gamma), delta_inv = Fe::pow_pm2(delta);
-  K.omega = fr_root_of_unity(K.logn); K.omega_inv = Fe::pow_pm2(K.omega);
-  K.n_inv = Fe::pow_pm2(cb::f_from_u64<Fe>(K.n));
-  K.coset = cb::f_from_u64<Fe>(5); K.coset_inv = Fe::pow_pm2(K.coset);
-  K.zinv = Fe::pow_pm2(Fe::sub(fr_pow_u64(K.coset, K.n), Fe::one()));
-  { Fe chk = fr_pow_u64(K.omega, K.n / 2); if (K.n > 1 && !Fe::add(chk, Fe::one()).is_zero()) return vz_fail(ctx, VIMZ_ERR_INVALID, "decider: root of unity"); }
+  if (!domain_constants(K, K.logn)) return vz_fail(ctx, VIMZ_ERR_INVALID, "decider: root of unity");
   // Lagrange basis at tau: L_j(tau) = Z(tau)/n · ω^j / (tau − ω^j)   (batch inversion)
   const Fe z_tau = Fe::sub(fr_pow_u64(tau, K.n), Fe::one());
   if (z_tau.is_zero()) return vz_fail(ctx, VIMZ_ERR_INVALID, "decider: tau lies in the domain");
@@ -512,12 +567,7 @@ int decider_setup_impl(vimz_cf* v, const uint64_t kzg_vk_g2[16], const Trapdoor&
     if (e != hipSuccess) return vz_fail(ctx, VIMZ_ERR_HIP, "decider: G2 key points", e);
     P_TRY(hipMalloc((void**)&K.b2_idx, 4 * std::max<size_t>(ix.size(), 1)));
     P_TRY(hipMemcpy(K.b2_idx, ix.data(), 4 * ix.size(), hipMemcpyHostToDevice)); }
-  // domain tables
-  P_TRY(hipMalloc((void**)&K.tw, 32 * (size_t)std::max<uint32_t>(K.n / 2, 1))); P_TRY(hipMalloc((void**)&K.tw_inv, 32 * (size_t)std::max<uint32_t>(K.n / 2, 1)));
-  { Fr w, wi; memcpy(w.v, K.omega.v, 32); memcpy(wi.v, K.omega_inv.v, 32);
-    hipLaunchKernelGGL(k_pow_table, dim3((K.n / 2 + 255) / 256), dim3(256), 0, s, K.tw, (size_t)K.n / 2, w);
-    hipLaunchKernelGGL(k_pow_table, dim3((K.n / 2 + 255) / 256), dim3(256), 0, s, K.tw_inv, (size_t)K.n / 2, wi);
-    P_TRY(hipGetLastError()); P_TRY(hipStreamSynchronize(s)); }
+  if ((rc = domain_tables(ctx, s, K))) return rc;
   // the few points of the verifying key, on the host
   K.alpha1 = to_affine(host_mul_fr<Fq>(g1, alpha)); K.beta1 = to_affine(host_mul_fr<Fq>(g1, beta)); K.delta1 = to_affine(host_mul_fr<Fq>(g1, delta));
   K.beta2 = to_affine(host_mul_fr<Fq2>(g2, beta)); K.gamma2 = to_affine(host_mul_fr<Fq2>(g2, gamma)); K.delta2 = to_affine(host_mul_fr<Fq2>(g2, delta));
@@ -830,6 +880,94 @@ int vimz_testing_decider_setup_seeded(vimz_cf* v, const uint64_t kzg_vk_g2[16], 
   if (!v || !out || (!seed && seed_len)) return VIMZ_ERR_INVALID;
   return decider_setup_impl(v, kzg_vk_g2, trapdoor_seeded(seed, seed_len), light != 0, out, seconds);
 }
+// ---- the decider's kernels on a caller's shapes (tests/test_gpu_g16_kernels.py): the functions the set-up and the prover call, over made-up inputs ----------
+}  // extern "C"
+namespace {
+// n scalars of 4 words (form = VIMZ_FORM_*) -> Montgomery elements; false: one of them is not below r
+bool g16_scalars_in(const uint64_t* src, size_t n, int form, std::vector<Fe>& out) {
+  out.resize(n);
+  for (size_t i = 0; i < n; i++) { Fe c; memcpy(c.v, src + 4 * i, 32); if (!c.is_reduced()) return false; out[i] = form == VIMZ_FORM_CANONICAL ? Fe::to_mont(c) : c; }
+  return true;
+}
+bool g16_form_ok(int form) { return form == VIMZ_FORM_CANONICAL || form == VIMZ_FORM_MONTGOMERY; }
+// s_i·gen for the scalars of `sc` as the set-up makes its key points: fixed_table on the host, fixed_base_batch on the device
+template <class F>
+int g16_fixed_mul(vimz_ctx* ctx, const Affine<F>& gen, const std::vector<Fe>& sc, std::vector<Affine<F>>& pts) {
+  std::lock_guard<std::mutex> g(ctx->mu);
+  P_TRY(hipSetDevice(ctx->device));
+  const std::vector<Affine<F>> T = fixed_table<F>(gen);
+  Affine<F>*dT = nullptr, *d_out = nullptr;
+  struct Free { Affine<F>**a, **b; ~Free() { if (*a) hipFree(*a); if (*b) hipFree(*b); } } fr{&dT, &d_out};
+  P_TRY(hipMalloc((void**)&dT, sizeof(Affine<F>) * T.size()));
+  P_TRY(hipMemcpy(dT, T.data(), sizeof(Affine<F>) * T.size(), hipMemcpyHostToDevice));
+  const hipError_t e = fixed_base_batch<F>(ctx->stream, sc, dT, &d_out);
+  if (e != hipSuccess) return vz_fail(ctx, VIMZ_ERR_HIP, "vimz_test_g16_fixed_mul", e);
+  pts.resize(sc.size());
+  P_TRY(hipMemcpy(pts.data(), d_out, sizeof(Affine<F>) * sc.size(), hipMemcpyDeviceToHost));
+  return VIMZ_OK;
+}
+}  // namespace
+extern "C" {
+int vimz_test_g16_domain(vimz_ctx* ctx, int logn, int what, const uint64_t* a, const uint64_t* b, const uint64_t* c, int form, uint64_t* out) {
+  if (!ctx || !a || !out || what < 0 || what > 3 || (what == 3 && (!b || !c)) || !g16_form_ok(form)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_g16_domain: bad argument");
+  if (logn < 1 || logn > 26) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_g16_domain: logn outside 1..26");      // (0: an empty grid and a shift by 32)
+  G16Key K;
+  if (!domain_constants(K, logn)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_g16_domain: root of unity");
+  const size_t n = K.n;
+  const int nv = what == 3 ? 3 : 1;
+  const uint64_t* src[3] = {a, b, c};
+  std::vector<Fe> in[3];
+  for (int q = 0; q < nv; q++) if (!g16_scalars_in(src[q], n, form, in[q])) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_g16_domain: a scalar is not below the modulus");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  P_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  uint32_t* dv[3] = {nullptr, nullptr, nullptr};
+  struct Free { G16Key* K; uint32_t** v; ~Free() { for (int q = 0; q < 3; q++) if (v[q]) hipFree(v[q]); free_key_raw(*K); } } fr{&K, dv};
+  { const int rc = domain_tables(ctx, s, K); if (rc) return rc; }
+  for (int q = 0; q < nv; q++) { P_TRY(hipMalloc((void**)&dv[q], 32 * n)); P_TRY(hipMemcpyAsync(dv[q], in[q].data(), 32 * n, hipMemcpyHostToDevice, s)); }
+  P_TRY(what == 0 ? ntt(s, dv[0], K, false) : what == 1 ? ntt(s, dv[0], K, true) : what == 2 ? coset_extend(s, dv[0], K) : quotient(s, dv, K));
+  P_TRY(hipMemcpyAsync(in[0].data(), dv[0], 32 * n, hipMemcpyDeviceToHost, s));
+  P_TRY(hipStreamSynchronize(s));
+  for (size_t i = 0; i < n; i++) { const Fe r = form == VIMZ_FORM_CANONICAL ? Fe::from_mont(in[0][i]) : in[0][i]; memcpy(out + 4 * i, r.v, 32); }
+  return VIMZ_OK;
+}
+int vimz_test_g16_fixed_mul(vimz_ctx* ctx, int group, const uint64_t* scalars, size_t n, uint64_t* out_xy) {
+  if (!ctx || !scalars || !out_xy || !n || n > (1u << 26) || (group != 1 && group != 2)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_g16_fixed_mul: bad argument");
+  std::vector<Fe> sc;
+  if (!g16_scalars_in(scalars, n, VIMZ_FORM_CANONICAL, sc)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_g16_fixed_mul: a scalar is not below the modulus");
+  if (group == 1) {
+    std::vector<G1Aff> pts;
+    const int rc = g16_fixed_mul<Fq>(ctx, g1_generator(), sc, pts); if (rc) return rc;
+    for (size_t i = 0; i < n; i++) { put_fq(out_xy + 8 * i, pts[i].x); put_fq(out_xy + 8 * i + 4, pts[i].y); }
+  } else {
+    std::vector<G2PAff> pts;
+    const int rc = g16_fixed_mul<Fq2>(ctx, g2_generator(), sc, pts); if (rc) return rc;
+    for (size_t i = 0; i < n; i++) put_g2(out_xy + 16 * i, pts[i]);
+  }
+  return VIMZ_OK;
+}
+int vimz_test_g16_g2_msm(vimz_ctx* ctx, const uint64_t* bases_xy, size_t n, const uint64_t* wires, size_t m, int form, const uint32_t* idx, uint64_t out_xy[16]) {
+  if (!ctx || !bases_xy || !wires || !idx || !out_xy || !g16_form_ok(form)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_g16_g2_msm: bad argument");
+  if (!n || n > m || m > (1u << 26)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_g16_g2_msm: needs 0 < n <= m <= 2^26");
+  for (size_t i = 0; i < n; i++) if (idx[i] >= m) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_g16_g2_msm: a wire number is not below m");
+  std::vector<G2PAff> pts(n);
+  for (size_t i = 0; i < n; i++) if (!get_g2(bases_xy + 16 * i, &pts[i])) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_g16_g2_msm: a coordinate is not below the modulus");
+  std::vector<Fe> z;
+  if (!g16_scalars_in(wires, m, form, z)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_g16_g2_msm: a scalar is not below the modulus");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  P_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  void* dev[4] = {nullptr, nullptr, nullptr, nullptr};      // bases, wires, wire numbers, canonical scalars
+  struct Free { void** v; ~Free() { for (int q = 0; q < 4; q++) if (v[q]) hipFree(v[q]); } } fr{dev};
+  const size_t bytes[4] = {sizeof(G2PAff) * n, 32 * m, 4 * n, 32 * n};
+  const void* src[3] = {pts.data(), z.data(), idx};
+  for (int q = 0; q < 4; q++) P_TRY(hipMalloc(&dev[q], bytes[q]));
+  for (int q = 0; q < 3; q++) P_TRY(hipMemcpyAsync(dev[q], src[q], bytes[q], hipMemcpyHostToDevice, s));
+  G2P sum;
+  { const int rc = g2_msm(ctx, s, (const G2PAff*)dev[0], (const uint32_t*)dev[1], (const uint32_t*)dev[2], (uint32_t)n, (uint32_t*)dev[3], &sum); if (rc) return rc; }
+  put_g2(out_xy, to_affine(sum));
+  return VIMZ_OK;
+}
 #endif
 
 // info = {constraints, wires, public inputs, domain size, non-zeros of A, B, C, rows of checks 5 and 6 (0: the light decider)}
@@ -936,11 +1074,7 @@ int vimz_decider_key_load(vimz_cf* v, const void* buf, size_t len, vimz_decider*
   for (G2PAff* p : {&K.beta2, &K.gamma2, &K.delta2}) { if (!get_g2(w + pos, p) || !g2_on_curve(*p) || !g2_in_subgroup(*p)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_decider_key_load: a G2 key point"); pos += 16; }
   K.ic.resize(K.n_pub + 1);
   for (auto& p : K.ic) { if (!get_g1(w + pos, &p) || !g1_on_curve(p)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_decider_key_load: an IC point"); pos += 8; }
-  // domain constants (as in the set-up)
-  K.omega = fr_root_of_unity(K.logn); K.omega_inv = Fe::pow_pm2(K.omega);
-  K.n_inv = Fe::pow_pm2(cb::f_from_u64<Fe>(K.n));
-  K.coset = cb::f_from_u64<Fe>(5); K.coset_inv = Fe::pow_pm2(K.coset);
-  K.zinv = Fe::pow_pm2(Fe::sub(fr_pow_u64(K.coset, K.n), Fe::one()));
+  if (!domain_constants(K, K.logn)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_decider_key_load: root of unity");
   std::lock_guard<std::mutex> g(ctx->mu);
   P_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
@@ -966,11 +1100,7 @@ int vimz_decider_key_load(vimz_cf* v, const void* buf, size_t len, vimz_decider*
     P_TRY(hipMemcpy(K.b2_q, b2.data(), sizeof(G2PAff) * b2.size(), hipMemcpyHostToDevice));
     P_TRY(hipMalloc((void**)&K.b2_idx, 4 * std::max<size_t>(ix.size(), 1)));
     P_TRY(hipMemcpy(K.b2_idx, ix.data(), 4 * ix.size(), hipMemcpyHostToDevice)); }
-  P_TRY(hipMalloc((void**)&K.tw, 32 * (size_t)std::max<uint32_t>(K.n / 2, 1))); P_TRY(hipMalloc((void**)&K.tw_inv, 32 * (size_t)std::max<uint32_t>(K.n / 2, 1)));
-  { Fr tw, twi; memcpy(tw.v, K.omega.v, 32); memcpy(twi.v, K.omega_inv.v, 32);
-    hipLaunchKernelGGL(k_pow_table, dim3((K.n / 2 + 255) / 256), dim3(256), 0, s, K.tw, (size_t)K.n / 2, tw);
-    hipLaunchKernelGGL(k_pow_table, dim3((K.n / 2 + 255) / 256), dim3(256), 0, s, K.tw_inv, (size_t)K.n / 2, twi);
-    P_TRY(hipGetLastError()); P_TRY(hipStreamSynchronize(s)); }
+  { const int rc = domain_tables(ctx, s, K); if (rc) return rc; }
   *out = d.release();
   return VIMZ_OK;
 }
@@ -1074,21 +1204,11 @@ int vimz_decider_prove(vimz_decider* d, vimz_cf* ivc, uint64_t* public_out, uint
   P_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   // h = (a·b − c) / Z on the coset 5·H
-  uint32_t* dv[3] = {nullptr, nullptr, nullptr}; uint32_t* dz = nullptr; G2P* dpart = nullptr;
-  struct Free { uint32_t** v; uint32_t** z; G2P** p; ~Free() { for (int q = 0; q < 3; q++) if (v[q]) hipFree(v[q]); if (*z) hipFree(*z); if (*p) hipFree(*p); } } fr{dv, &dz, &dpart};
+  uint32_t* dv[3] = {nullptr, nullptr, nullptr}; uint32_t* dz = nullptr;
+  struct Free { uint32_t** v; uint32_t** z; ~Free() { for (int q = 0; q < 3; q++) if (v[q]) hipFree(v[q]); if (*z) hipFree(*z); } } fr{dv, &dz};
   for (int q = 0; q < 3; q++) { P_TRY(hipMalloc((void**)&dv[q], 32 * (size_t)K.n)); P_TRY(hipMemcpyAsync(dv[q], abc[q].data(), 32 * (size_t)K.n, hipMemcpyHostToDevice, s)); }
   P_TRY(hipMalloc((void**)&dz, 32 * (size_t)K.m)); P_TRY(hipMemcpyAsync(dz, z.data(), 32 * (size_t)K.m, hipMemcpyHostToDevice, s));
-  auto asFr = [](const Fe& x) { Fr r; memcpy(r.v, x.v, 32); return r; };
-  const unsigned gb = (K.n + 255) / 256;
-  for (int q = 0; q < 3; q++) {
-    P_TRY(ntt(s, dv[q], K, true));
-    hipLaunchKernelGGL(k_scale_pow, dim3(gb), dim3(256), 0, s, dv[q], K.n, asFr(K.n_inv), asFr(K.coset));
-    P_TRY(ntt(s, dv[q], K, false));
-  }
-  hipLaunchKernelGGL(k_quotient, dim3(gb), dim3(256), 0, s, dv[0], (const uint32_t*)dv[1], (const uint32_t*)dv[2], K.n, asFr(K.zinv));
-  P_TRY(ntt(s, dv[0], K, true));
-  hipLaunchKernelGGL(k_scale_pow, dim3(gb), dim3(256), 0, s, dv[0], K.n, asFr(K.n_inv), asFr(K.coset_inv));
-  P_TRY(hipGetLastError()); P_TRY(hipStreamSynchronize(s));
+  P_TRY(quotient(s, dv, K)); P_TRY(hipStreamSynchronize(s));
   const double t_ntt = now_s();
   // the multi-scalar multiplications
   uint64_t pt[8];
@@ -1112,16 +1232,7 @@ int vimz_decider_prove(vimz_decider* d, vimz_cf* ivc, uint64_t* public_out, uint
   G2P sb2 = G2P::identity();
   if (K.n_b2) {
     if ((size_t)K.n_b2 > (size_t)K.n) return vz_fail(ctx, VIMZ_ERR_INVALID, "decider: the G2 query is longer than the domain");
-    P_TRY(hipMalloc((void**)&dpart, sizeof(G2P) * ((size_t)G2_PLANES * G2_PLANE_THREADS + G2_PLANES)));
-    G2P* dsum = dpart + (size_t)G2_PLANES * G2_PLANE_THREADS;
-    hipLaunchKernelGGL(k_g2_canon, dim3((K.n_b2 + 255) / 256), dim3(256), 0, s, (const uint32_t*)dz, (const uint32_t*)K.b2_idx, K.n_b2, dv[1]);
-    hipLaunchKernelGGL(k_g2_planes, dim3(G2_PLANE_THREADS / 256, G2_PLANES), dim3(256), 0, s, (const G2PAff*)K.b2_q, (const uint32_t*)dv[1], K.n_b2, dpart);
-    hipLaunchKernelGGL(k_g2_plane_tree, dim3(G2_PLANES), dim3(128), 0, s, (const G2P*)dpart, dsum);
-    P_TRY(hipGetLastError());
-    std::vector<G2P> planes(G2_PLANES);
-    P_TRY(hipMemcpyAsync(planes.data(), dsum, sizeof(G2P) * G2_PLANES, hipMemcpyDeviceToHost, s));
-    P_TRY(hipStreamSynchronize(s));
-    for (int j = (int)G2_PLANES - 1; j >= 0; j--) { sb2 = dbl(sb2); add_full(sb2, planes[j]); }
+    if ((rc = g2_msm(ctx, s, K.b2_q, dz, K.b2_idx, K.n_b2, dv[1], &sb2))) return rc;
   }
   lap("msm b2 (G2)");
   const double t_msm = now_s();
