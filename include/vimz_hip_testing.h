@@ -81,6 +81,17 @@ int vimz_test_g16_fixed_mul(vimz_ctx* ctx, int group, const uint64_t* scalars, s
 /* the proof's G2 multi-scalar multiplication on a caller's query: sum of wires[idx[i]]·P_i over n >= 1 points of G2 (canonical, 16 words each, the identity as
  * zeros), m >= n wire values of 4 words (form = VIMZ_FORM_*) and n wire numbers below m.  out_xy: the affine sum, canonical, the identity as zeros. */
 int vimz_test_g16_g2_msm(vimz_ctx* ctx, const uint64_t* bases_xy, size_t n, const uint64_t* wires, size_t m, int form, const uint32_t* idx, uint64_t out_xy[16]);
+/* The chains of the full decider's check 5 (vimz_amd/csrc/aug/decider_cf.hpp: every scalar walks the 127 two-bit windows of its generator's table by affine
+ * additions from the derived generator H) over a caller's generators and scalars, through the functions the prover calls: where = 0 the host's
+ * (cf_open_chains_host; ctx may be NULL), where = 1 the device's (k_cf_open_chains, the scalars uploaded in Montgomery form as the prover holds them, both
+ * openings of one launch filled with them).  gens_xy: n_gens affine points of Grumpkin, canonical, 8 words each (the key is built by CfOpeningKey::build);
+ * scalars: cnt <= n_gens canonical scalars below q, scalar k over generator k.  wires_out: cnt·127·4 elements (b0·b1, slope, x, y per window), ends_out: cnt
+ * points, h_out: H — all canonical.  *bad_out = 1: an addition met two points with the same x (the wires are then unspecified). */
+int vimz_test_decider_chains(vimz_ctx* ctx, int where, const uint64_t* gens_xy, size_t n_gens, const uint64_t* scalars, size_t cnt, uint64_t* wires_out,
+                             uint64_t* ends_out, uint64_t h_out[8], int* bad_out);
+/* the full assignment z (canonical, 4 words per wire) of the decider circuit as vimz_decider_prove builds it for the proof `ivc` holds, check 5's chains from
+ * the host (chains_on_gpu = 0) or from the device.  Returns the byte size (copies when buf is large enough); negative: vimz_decider_prove's error codes. */
+int64_t vimz_testing_decider_witness(vimz_decider* d, vimz_cf* ivc, int chains_on_gpu, void* buf, size_t cap);
 
 #ifdef __cplusplus
 }

@@ -110,12 +110,50 @@ struct W5 {
   static W5 inv_odd(const W5& m) { W5 x = zero(); x.w[0] = 1; W5 two = zero(); two.w[0] = 2; for (int it = 0; it < 9; it++) x = mul(x, sub(two, mul(m, x))); return x; }
 };
 
+// ---- the chains of check 5 in witness mode: every scalar's 127 affine additions from H over its key's window table ----------------------------------
+// wires [k][j][4] = (b0·b1, slope, x, y) of window j of scalar k, in the order open_chains allocates them; ends[k] = the chain's last point.
+// One batched inversion per window over all the scalars.  false: some addition met two points with the same x (the wires are then unspecified).
+// The device's version of the same values: k_cf_open_chains (decider_chains.hip).
+inline bool cf_open_chains_host(const CfOpeningKey& key, const U256w* vals, uint32_t cnt, CfFr* wires, Affine<CfFr>* ends) {
+  typedef CfFr F;
+  auto bit_of = [](const U256w& v, int k) { return k < 256 && ((v.w[k >> 6] >> (k & 63)) & 1u); };
+  bool ok = true;
+  std::vector<Affine<F>> acc(cnt, key.H);
+  std::vector<F> den(cnt);
+  for (int j = 0; j < CFO_WINDOWS; j++) {
+    for (uint32_t k = 0; k < cnt; k++) {
+      const int d = (int)bit_of(vals[k], 2 * j) + 2 * (int)bit_of(vals[k], 2 * j + 1);
+      den[k] = F::sub(key.entry(k, j, d).x, acc[k].x);
+      if (den[k].is_zero()) ok = false;
+    }
+    batch_inv(den);
+    for (uint32_t k = 0; k < cnt; k++) {
+      const bool b0 = bit_of(vals[k], 2 * j), b1 = bit_of(vals[k], 2 * j + 1);
+      const Affine<F>& q = key.entry(k, j, (int)b0 + 2 * (int)b1);
+      const F lam = F::mul(F::sub(q.y, acc[k].y), den[k]);
+      Affine<F> r;
+      r.x = F::sub(F::sub(F::sqr(lam), acc[k].x), q.x);
+      r.y = F::sub(F::mul(lam, F::sub(acc[k].x, r.x)), acc[k].y);
+      F* o = &wires[((size_t)k * CFO_WINDOWS + j) * 4];
+      o[0] = (b0 && b1) ? F::one() : F::zero(); o[1] = lam; o[2] = r.x; o[3] = r.y;
+      acc[k] = r;
+    }
+  }
+  for (uint32_t k = 0; k < cnt; k++) ends[k] = acc[k];
+  return ok;
+}
+struct CfChainValues { const CfFr* wires = nullptr; const Affine<CfFr>* ends = nullptr; };      // one opening's chains, computed elsewhere
+
 // ---- the gadgets ----------------------------------------------------------------------------------------------------------------------------------
 struct CfFullIn {
   const CfOpeningKey* key = nullptr;
   const cb::BuilderT<CfFq>* shape = nullptr;           // the CycleFold circuit
   const CfFq* W = nullptr;                              // the running CycleFold witness: wires 1 .. n_w-1-CF_IO of Z (Montgomery); nullptr: shape mode / zeros
   const CfFq* E = nullptr;                              // its error vector
+  // optional: the chains of check 5 for W and for E as the device computed them (Montgomery, canonical).  chains_wait, when set, is called once with
+  // chains_wait_arg where check 5 begins — the values need not be there before; false: an addition met two points with the same x (the statement is then flagged)
+  CfChainValues chW, chE;
+  bool (*chains_wait)(void*) = nullptr; void* chains_wait_arg = nullptr;
 };
 
 struct DeciderCfGadget {
@@ -136,40 +174,21 @@ struct DeciderCfGadget {
   // ---- check 5: Σ_k s_k·G_k from the scalars' bits (bits[k*254 + i]); returns the sum's chain value  H2 + cnt·H + Σ(s_k + off)·G_k  as (x, y) ----
   struct XY { N x, y; };
   struct ChainTemplate { bool have = false; uint32_t row0 = 0, bits0 = 0, chain0 = 0, cnt = 0; } tmpl;      // shape mode: the first opening's rows, to copy from
-  XY open_chains(const CfOpeningKey& key, const std::vector<N>& bits, const U256w* vals /* witness mode: the scalars */, uint32_t cnt) {
+  XY open_chains(const CfOpeningKey& key, const std::vector<N>& bits, const U256w* vals /* witness mode: the scalars */, uint32_t cnt, const CfChainValues* pre = nullptr) {
     const bool sh = shape();
-    // witness mode: all the chains' values at once, one batched inversion per window
-    std::vector<F> wv;                                   // [k][j][4]: product, slope, x, y
-    std::vector<Affine<F>> S(cnt);
-    if (!sh) {
-      wv.resize((size_t)cnt * CFO_WINDOWS * 4);
-      std::vector<Affine<F>> acc(cnt, key.H);
-      std::vector<F> den(cnt);
-      for (int j = 0; j < CFO_WINDOWS; j++) {
-        for (uint32_t k = 0; k < cnt; k++) {
-          const int d = (int)bit_of(vals[k], 2 * j) + 2 * (int)bit_of(vals[k], 2 * j + 1);
-          den[k] = F::sub(key.entry(k, j, d).x, acc[k].x);
-          if (den[k].is_zero()) cs.bad = true;
-        }
-        batch_inv(den);
-        for (uint32_t k = 0; k < cnt; k++) {
-          const bool b0 = bit_of(vals[k], 2 * j), b1 = bit_of(vals[k], 2 * j + 1);
-          const Affine<F>& q = key.entry(k, j, (int)b0 + 2 * (int)b1);
-          const F lam = F::mul(F::sub(q.y, acc[k].y), den[k]);
-          Affine<F> r;
-          r.x = F::sub(F::sub(F::sqr(lam), acc[k].x), q.x);
-          r.y = F::sub(F::mul(lam, F::sub(acc[k].x, r.x)), acc[k].y);
-          F* o = &wv[((size_t)k * CFO_WINDOWS + j) * 4];
-          o[0] = (b0 && b1) ? F::one() : F::zero(); o[1] = lam; o[2] = r.x; o[3] = r.y;
-          acc[k] = r;
-        }
-      }
-      S = acc;
+    // witness mode: all the chains' values at once — computed here (cf_open_chains_host) or handed in (the device's: decider_chains.hpp)
+    std::vector<F> wv_own; std::vector<Affine<F>> S_own;
+    const F* wv = pre ? pre->wires : nullptr;            // [k][j][4]: product, slope, x, y
+    const Affine<F>* S = pre ? pre->ends : nullptr;
+    if (!sh && !pre) {
+      wv_own.resize((size_t)cnt * CFO_WINDOWS * 4); S_own.resize(cnt);
+      if (!cf_open_chains_host(key, vals, cnt, wv_own.data(), S_own.data())) cs.bad = true;
+      wv = wv_own.data(); S = S_own.data();
     }
     std::vector<XY> Sn(cnt);
     for (uint32_t k = 0; k < cnt; k++) {
       if (!sh) {      // the chain's wires, in the order the shape allocates them
-        cs.w.insert(cs.w.end(), wv.begin() + (size_t)k * CFO_WINDOWS * 4, wv.begin() + (size_t)(k + 1) * CFO_WINDOWS * 4);
+        cs.w.insert(cs.w.end(), wv + (size_t)k * CFO_WINDOWS * 4, wv + (size_t)(k + 1) * CFO_WINDOWS * 4);
         Sn[k].x.v = S[k].x; Sn[k].y.v = S[k].y;
         continue;
       }
@@ -531,8 +550,10 @@ struct DeciderCfGadget {
     lap("bits");
     // check 5
     Ec ec(cs, CycleSide<BnFr>::b(), CycleSide<BnFr>::G());
-    auto opened = [&](const std::vector<N>& bits, const U256w* vals, uint32_t cnt, const N& cx_, const N& cy_) {
-      XY tot = open_chains(*in.key, bits, vals, cnt);
+    const bool pre = have && in.chW.wires && in.chW.ends && in.chE.wires && in.chE.ends;
+    if (pre && in.chains_wait && !in.chains_wait(in.chains_wait_arg)) cs.bad = true;
+    auto opened = [&](const std::vector<N>& bits, const U256w* vals, uint32_t cnt, const N& cx_, const N& cy_, const CfChainValues& ch) {
+      XY tot = open_chains(*in.key, bits, vals, cnt, pre ? &ch : nullptr);
       const Affine<F> K = in.key->offset(cnt);
       Ec::Pt cm; cm.x = cx_; cm.y = cy_; cm.inf = cs.is_zero(cm.y);
       Ec::Pt kc; kc.x = cs.constant(K.x); kc.y = cs.constant(K.y); kc.inf = cs.zero();
@@ -540,9 +561,9 @@ struct DeciderCfGadget {
       cs.enforce_equal(s.x, tot.x); cs.enforce_equal(s.y, tot.y);
       if (!cs.b && (!s.x.v.eq(tot.x.v) || !s.y.v.eq(tot.y.v))) cs.bad = true;
     };
-    opened(wbits, wv.data(), nW, cWx, cWy);
+    opened(wbits, wv.data(), nW, cWx, cWy, in.chW);
     lap("opening of cmW");
-    opened(ebits, ev.data(), nE, cEx, cEy);
+    opened(ebits, ev.data(), nE, cEx, cEy, in.chE);
     lap("opening of cmE");
     // check 6: z = (u, W, x) as integers
     std::vector<Big> z(sh.n_wires);

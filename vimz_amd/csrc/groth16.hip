@@ -16,6 +16,7 @@
 #include "cyclefold_internal.hpp"
 #include "decider_view.hpp"
 #include "aug/decider.hpp"
+#include "decider_chains.hpp"
 #include "pairing.hpp"
 #include "vecops_api.hpp"
 #ifdef VIMZ_TESTING
@@ -23,6 +24,9 @@
 #endif
 
 namespace {
+
+// check 5's chains of the full decider: on the device unless VIMZ_DECIDER_CHAINS=host (profiles/decider_chains.txt: the measurement the default follows)
+constexpr bool DECIDER_CHAINS_GPU_DEFAULT = true;
 
 // Secrets are wiped when they go out of scope: the trapdoor, everything derived from it that still determines it (powers of tau, the
 // Lagrange basis at tau, the query scalars), a proof's blinders.
@@ -202,7 +206,27 @@ struct vimz_decider {
   G16Key key;
   G2PAff kzg_vk;                         // [tau]G2 of the SRS the prover's ck_main is made of (identity: not given — KZG checks are refused)
   double setup_s[4] = {0, 0, 0, 0};      // circuit synthesis, QAP evaluation at the trapdoor (host), key points (GPU), total
-  ~vimz_decider() { if (ctx) { hipSetDevice(ctx->device); free_key_raw(key); } }      // (error paths of the setup end here too)
+  // Full decider only (a light one allocates none of it): check 5's chains on the device — the opening key's window table, the kernel's outputs, their
+  // pinned copies on the host, a stream of its own (the kernel runs beside the prover's final fold) and the two events that time it.  mu: one prove at a time uses them,
+  // from before its final fold until its witness is done; taken BEFORE the context's lock, never while holding it.
+  struct Chains {
+    CfChainsKey key;
+    uint32_t nW = 0, nE = 0;
+    uint32_t* dev = nullptr;             // wires of W's and E's chains, their end points, the flag
+    uint32_t* host = nullptr;            // the same, pinned
+    hipStream_t stream = nullptr; hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    std::mutex mu;
+    size_t wire_words() const { return CF_CHAIN_WORDS * ((size_t)nW + nE); }
+    size_t words() const { return wire_words() + 16 * ((size_t)nW + nE) + 1; }
+  } chains;
+  void free_chains() {
+    cf_chains_key_free(chains.key);
+    if (chains.dev) hipFree(chains.dev); if (chains.host) hipHostFree(chains.host);
+    if (chains.ev0) hipEventDestroy(chains.ev0); if (chains.ev1) hipEventDestroy(chains.ev1);
+    if (chains.stream) hipStreamDestroy(chains.stream);
+    chains.dev = chains.host = nullptr; chains.ev0 = chains.ev1 = nullptr; chains.stream = nullptr;
+  }
+  ~vimz_decider() { if (ctx) { hipSetDevice(ctx->device); free_key_raw(key); free_chains(); } }      // (error paths of the setup end here too; vimz_decider_free)
 };
 
 namespace {
@@ -409,8 +433,9 @@ int kzg_setup_impl(vimz_ctx* ctx, const Fe& tau, size_t n, vimz_bases** srs_out,
 
 // the decider circuit for this prover's shapes: light (checks 1-4) or full (also the CycleFold instance's commitments and relation: the first
 // generators of the prover's CycleFold commitment key become constants of the circuit)
-int decider_circuit_build(vimz_cf* v, bool light, aug::DeciderCircuit& circ) {
+int decider_circuit_build(vimz_cf* v, bool light, vimz_decider& dec) {
   vimz_ctx* ctx = v->ctx;
+  aug::DeciderCircuit& circ = dec.circ;
   const cb::BuilderT<Fe>& main = v->circ->build->b;
   std::vector<G2Aff> gens;
   if (!light) {
@@ -435,6 +460,15 @@ int decider_circuit_build(vimz_cf* v, bool light, aug::DeciderCircuit& circ) {
     if (light) circ.finish(main, v->c1->len_z);
     else circ.finish(main, v->c1->len_z, &v->cf.b, gens.data(), (uint32_t)gens.size());
   } catch (const std::exception& e) { return vz_fail(ctx, VIMZ_ERR_INVALID, e.what()); }
+  if (!light) {      // check 5's chains on the device: the window table once (43 MB at 1 313 generators), on the stream the chains will run on — not the context's, as above
+    vimz_decider::Chains& ch = dec.chains;
+    ch.nW = v->cf.b.n_wires - 1 - aug::CF_IO; ch.nE = v->cf.b.n_constraints();
+    P_TRY(hipStreamCreateWithFlags(&ch.stream, hipStreamNonBlocking));
+    P_TRY(hipEventCreate(&ch.ev0)); P_TRY(hipEventCreate(&ch.ev1));
+    P_TRY(cf_chains_key_upload(ch.stream, circ.okey, ch.key));
+    P_TRY(hipMalloc((void**)&ch.dev, 4 * ch.words()));
+    P_TRY(hipHostMalloc((void**)&ch.host, 4 * ch.words()));
+  }
   return VIMZ_OK;
 }
 // [tau]G2 given with a prover whose main key is not the SRS it belongs to makes every later KZG check fail far from its cause:
@@ -477,7 +511,7 @@ int decider_setup_impl(vimz_cf* v, const uint64_t kzg_vk_g2[16], const Trapdoor&
     const int rcv = kzg_vk_matches_srs(v, d->kzg_vk, "vimz_decider_setup");
     if (rcv) return rcv;
   }
-  { const int rcb = decider_circuit_build(v, light, d->circ); if (rcb) return rcb; }
+  { const int rcb = decider_circuit_build(v, light, *d); if (rcb) return rcb; }
   const double t_syn = now_s();
   G16Key& K = d->key;
   const cb::BuilderT<Fe>& b = d->circ.b;
@@ -672,8 +706,9 @@ void vimz_decider_free(vimz_decider* d) {
     std::unique_lock<std::mutex> g(d->ctx->mu);
     hipSetDevice(d->ctx->device);
     hipStreamSynchronize(d->ctx->stream);
+    if (d->chains.stream) hipStreamSynchronize(d->chains.stream);
   }
-  delete d;
+  delete d;      // (~vimz_decider: the key's points and, for a full decider, the chains' table and buffers)
 }
 
 // KZG::setup (Sonobe's `KZG::setup(rng, n)` inside vimz/src/sonobe_backend/folding.rs:36-48 `prepare_folding`): tau from the OS, used and forgotten
@@ -1053,7 +1088,7 @@ int vimz_decider_key_load(vimz_cf* v, const void* buf, size_t len, vimz_decider*
   if (nwords < G16_KEY_HEADER + 4 + 16 + 24 + 48 || w[0] != G16_KEY_MAGIC || w[6] > 1) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_decider_key_load: not a decider key");
   std::unique_ptr<vimz_decider> d(new vimz_decider());
   d->vk = v; d->ctx = ctx;
-  { const int rcb = decider_circuit_build(v, w[6] == 1, d->circ); if (rcb) return rcb; }
+  { const int rcb = decider_circuit_build(v, w[6] == 1, *d); if (rcb) return rcb; }
   G16Key& K = d->key;
   const cb::BuilderT<Fe>& b = d->circ.b;
   K.m = b.n_wires; K.n_pub = d->circ.n_public; K.n_c = b.n_constraints();
@@ -1105,38 +1140,81 @@ int vimz_decider_key_load(vimz_cf* v, const void* buf, size_t len, vimz_decider*
   return VIMZ_OK;
 }
 
-// Decider::prove (mod.rs:76-78) for the IVC proof `ivc` holds after i >= 1 steps (left unchanged): the final fold U_{i+1} = NIFS(U_i, u_i) on the GPU
-// (cross term, its commitment, the challenge of aug/decider.hpp, the folded witness and error vector), the KZG openings of U_{i+1}'s two commitments at
-// the challenges that follow from them, and the Groth16 proof of the decider circuit — ALL 25 calldata words (contracts/*Verifier.sol:785-810;
-// vimz_amd/calldata.py names them), canonical, 4 little-endian limbs each.  public_out: the info[2] public inputs (canonical), as the contract
-// assembles them from the words.  VIMZ_ERR_UNSAT when the IVC proof does not satisfy the decider's statement.
-// seconds (optional) = {final fold + KZG openings (GPU), witness + sparse products (host), NTTs, MSMs, total, 0}.
-int vimz_decider_prove(vimz_decider* d, vimz_cf* ivc, uint64_t* public_out, uint64_t words_out[100], double seconds[6]) {
-  if (!d || !ivc || !public_out || !words_out) return VIMZ_ERR_INVALID;
+// What vimz_decider_prove does up to the decider circuit's assignment: the final fold U_{i+1} = NIFS(U_i, u_i) and the KZG openings on the GPU, then the witness
+// z of the decider circuit on the host.  chains_gpu (full decider): check 5's chains come from k_cf_open_chains instead of the host's loop.
+}  // extern "C"
+namespace {
+struct DeciderWitness {
+  std::vector<Fe> z;
+  G1Aff cmT; uint32_t r_low[4]; uint64_t kzg_out[2][12];      // kzg_out: eval (4), proof (8)
+  Fe cW, cE;
+  double t_fold = 0, chains_gpu_s = 0;
+};
+// VIMZ_DECIDER_CHAINS = host | gpu, read per call (a debugging switch like the others); unset: the default
+int decider_chains_mode(vimz_ctx* ctx, bool* gpu) {
+  const char* e = getenv("VIMZ_DECIDER_CHAINS");
+  if (!e || !*e) { *gpu = DECIDER_CHAINS_GPU_DEFAULT; return VIMZ_OK; }
+  if (!strcmp(e, "gpu")) { *gpu = true; return VIMZ_OK; }
+  if (!strcmp(e, "host")) { *gpu = false; return VIMZ_OK; }
+  return vz_fail(ctx, VIMZ_ERR_INVALID, "VIMZ_DECIDER_CHAINS must be host or gpu");
+}
+// Check 5's chains while they are in flight on the decider's own stream: wait() where check 5 begins (CfFullIn::chains_wait), and whichever way decider_witness
+// is left the stream is idle before the lock on the decider's buffers is given up — the kernel reads the IVC's vectors, the download writes the pinned block.
+struct ChainsInFlight {
+  vimz_decider::Chains* c = nullptr;      // set once work of this call may be queued
+  bool waited = false; hipError_t err = hipSuccess; double seconds = 0;
+  bool wait() {      // false: an addition met two points with the same x, or the device failed (err)
+    waited = true;
+    if ((err = hipEventSynchronize(c->ev1)) != hipSuccess) return false;
+    float ms = 0; if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) seconds = 1e-3 * ms;
+    return c->host[c->words() - 1] == 0;
+  }
+  static bool wait_cb(void* self) { return ((ChainsInFlight*)self)->wait(); }
+  void drain() { if (c && !waited) { waited = true; err = hipStreamSynchronize(c->stream); } }
+  ~ChainsInFlight() { drain(); }
+};
+int decider_witness(vimz_decider* d, vimz_cf* ivc, bool chains_gpu, DeciderWitness& out) {
   vimz_ctx* ctx = d->ctx; vimz_cf* v = d->vk;
-  const G16Key& K = d->key;
-  const double t_all = now_s();
   if (ivc->ctx != ctx || ivc->pri->n_wires != v->pri->n_wires || ivc->pri->n_c != v->pri->n_c || !ivc->c1->digest.eq(v->c1->digest) || ivc->ck1 != v->ck1)
     return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_decider_prove: the IVC proof belongs to other shapes / keys than the decider was set up for");
   if (ivc->broken) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_decider_prove: the IVC failed in the middle of a step");
   if (ivc->i == 0) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_decider_prove: the IVC has no steps");
+  if (d->circ.full && (ivc->ck2 != v->ck2 || ivc->sec.n_w != v->cf.b.n_wires || ivc->sec.n_c != v->cf.b.n_constraints()))
+    return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_decider_prove: the IVC proof's CycleFold key / shape is not the one the full decider was set up for");
+  chains_gpu = chains_gpu && d->circ.full;
   vimz_prover* p = ivc->pri;
   const size_t nw = p->n_wires, nc = p->n_c;
   std::vector<Fe> Wf(nw), Ef(nc);
   aug::DeciderIn in;
-  G1Aff cmT, cWn, cEn;
-  uint32_t r_low[4];
-  uint64_t kzg_out[2][12];      // eval (4), proof (8)
-  Fe cW, cE;
+  G1Aff cWn, cEn;
+  G1Aff& cmT = out.cmT; uint32_t* r_low = out.r_low; uint64_t (*kzg_out)[12] = out.kzg_out; Fe &cW = out.cW, &cE = out.cE;
+  // the decider's chain buffers are this call's until it returns.  Lock order: the chains' lock, then the context's — never the other way round
+  vimz_decider::Chains& chains = d->chains;
+  std::unique_lock<std::mutex> chains_lock;
+  if (chains_gpu) chains_lock = std::unique_lock<std::mutex>(chains.mu);
+  ChainsInFlight flight;
+  // (the final fold's vectors are released when this function returns, not where their block ends: hipFree waits for the whole device, the chains' kernel on its
+  //  own stream included — presumably why the fold's span was 35 ms longer with the chains on the device in profiles/decider_chains.txt, which predates this)
+  uint32_t* dev = nullptr;
+  struct FreeDev { uint32_t** q; ~FreeDev() { if (*q) hipFree(*q); } } fd{&dev};
   {
     std::lock_guard<std::mutex> g(ctx->mu);
     P_TRY(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     for (hipStream_t q : {ivc->s2, ivc->s3, ivc->s4}) if (q) P_TRY(hipStreamSynchronize(q));
     P_TRY(hipStreamSynchronize(s));
-    uint32_t* dev = nullptr;
+    if (chains_gpu) {
+      // check 5's chains (full decider): the running CycleFold witness (wires 1 .. of Z) and error vector are final once the streams above are idle — both openings
+      // in one launch on the decider's own stream, beside the final fold below; the values come home into pinned memory and are waited for where check 5 begins
+      const SecDev& S = ivc->sec;
+      uint32_t *d_wi = chains.dev, *d_en = d_wi + chains.wire_words(), *d_bad = chains.dev + chains.words() - 1;
+      flight.c = &chains;
+      P_TRY(hipEventRecord(chains.ev0, chains.stream));
+      P_TRY(cf_chains_launch(chains.stream, chains.key, S.Zrun + 8, chains.nW, S.E, chains.nE, d_wi, d_en, d_bad));
+      P_TRY(hipMemcpyAsync(chains.host, chains.dev, 4 * chains.words(), hipMemcpyDeviceToHost, chains.stream));
+      P_TRY(hipEventRecord(chains.ev1, chains.stream));
+    }
     P_TRY(hipMalloc((void**)&dev, 32 * (nw + 2 * nc)));
-    struct FreeDev { uint32_t* q; ~FreeDev() { hipFree(q); } } fd{dev};
     uint32_t *Wd = dev, *Ed = dev + 8 * nw, *Td = Ed + 8 * nc;
     P_TRY(hipMemcpyAsync(Wd, p->Zrun, 32 * nw, hipMemcpyDeviceToDevice, s));
     P_TRY(hipMemcpyAsync(Ed, p->E, 32 * nc, hipMemcpyDeviceToDevice, s));
@@ -1168,7 +1246,7 @@ int vimz_decider_prove(vimz_decider* d, vimz_cf* ivc, uint64_t* public_out, uint
     P_TRY(hipMemcpyAsync(Ef.data(), Ed, 32 * nc, hipMemcpyDeviceToHost, s));
     P_TRY(hipStreamSynchronize(s));
   }
-  const double t_fold = now_s();
+  out.t_fold = now_s();
   in.i = ivc->i; in.z0 = ivc->z0; in.zi = p->z_cur;
   in.U = ivc->U; in.u = ivc->u; in.cfU = ivc->cfU;
   { Fe c; memcpy(c.v, kzg_out[0], 32); in.eW = Fe::to_mont(c); memcpy(c.v, kzg_out[1], 32); in.eE = Fe::to_mont(c); }
@@ -1176,8 +1254,6 @@ int vimz_decider_prove(vimz_decider* d, vimz_cf* ivc, uint64_t* public_out, uint
   std::vector<Fq> cfZ, cfE;
   if (d->circ.full) {      // checks 5 and 6: the running CycleFold pair's witness and error vector
     const SecDev& S = ivc->sec;
-    if (ivc->ck2 != v->ck2 || S.n_w != v->cf.b.n_wires || S.n_c != v->cf.b.n_constraints())
-      return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_decider_prove: the IVC proof's CycleFold key / shape is not the one the full decider was set up for");
     cfZ.resize(S.n_w); cfE.resize(S.n_c);
     std::lock_guard<std::mutex> g(ctx->mu);
     P_TRY(hipSetDevice(ctx->device));
@@ -1186,14 +1262,48 @@ int vimz_decider_prove(vimz_decider* d, vimz_cf* ivc, uint64_t* public_out, uint
     P_TRY(hipStreamSynchronize(ctx->stream));
     in.full.W = cfZ.data() + 1; in.full.E = cfE.data();
   }
+  if (chains_gpu) {
+    const Fe* wires = (const Fe*)chains.host; const G2Aff* ends = (const G2Aff*)(chains.host + chains.wire_words());
+    in.full.chW.wires = wires; in.full.chW.ends = ends;
+    in.full.chE.wires = wires + (size_t)chains.nW * aug::CFO_WINDOWS * 4; in.full.chE.ends = ends + chains.nW;
+    in.full.chains_wait = &ChainsInFlight::wait_cb; in.full.chains_wait_arg = &flight;
+  }
   // (the main relation's rows are a third of the witness's time when evaluated one by one inside the circuit: their products come from the host's threads)
   std::vector<Fe> pre_abc[3];
   host_spmv3(v->circ->build->b, Wf, pre_abc);
   in.pre_az = pre_abc[0].data(); in.pre_bz = pre_abc[1].data(); in.pre_cz = pre_abc[2].data(); in.pre_z = Wf.data();
-  std::vector<Fe> z;
+  std::vector<Fe>& z = out.z;
   bool bad = false;
   try { z = d->circ.witness(v->circ->build->b, in, &bad); } catch (const std::exception& e) { return vz_fail(ctx, VIMZ_ERR_INVALID, e.what()); }
+  flight.drain();      // (check 5 was never reached: its error, if any, is still this call's)
+  out.chains_gpu_s = flight.seconds;
+  if (flight.err != hipSuccess) return vz_fail(ctx, VIMZ_ERR_HIP, "vimz_decider_prove: the chains of check 5 on the device", flight.err);
   if (bad) return vz_fail(ctx, VIMZ_ERR_UNSAT, "vimz_decider_prove: the IVC proof does not satisfy the decider's statement (hashes, relaxed relations, CycleFold commitments or KZG evaluations)");
+  return VIMZ_OK;
+}
+}  // namespace
+extern "C" {
+
+// Decider::prove (mod.rs:76-78) for the IVC proof `ivc` holds after i >= 1 steps (left unchanged): the final fold U_{i+1} = NIFS(U_i, u_i) on the GPU
+// (cross term, its commitment, the challenge of aug/decider.hpp, the folded witness and error vector), the KZG openings of U_{i+1}'s two commitments at
+// the challenges that follow from them, and the Groth16 proof of the decider circuit — ALL 25 calldata words (contracts/*Verifier.sol:785-810;
+// vimz_amd/calldata.py names them), canonical, 4 little-endian limbs each.  public_out: the info[2] public inputs (canonical), as the contract
+// assembles them from the words.  VIMZ_ERR_UNSAT when the IVC proof does not satisfy the decider's statement.
+// seconds (optional) = {final fold + KZG openings (GPU), witness + sparse products (host), NTTs, MSMs, total, check 5's chains on the GPU}.
+// The last one: kernel and download of k_cf_open_chains by the device's clock (they run beside the first two spans, not after them); 0 when the chains
+// are made on the host — the light decider, or VIMZ_DECIDER_CHAINS=host (=gpu: on the device; read per call; unset: gpu).
+int vimz_decider_prove(vimz_decider* d, vimz_cf* ivc, uint64_t* public_out, uint64_t words_out[100], double seconds[6]) {
+  if (!d || !ivc || !public_out || !words_out) return VIMZ_ERR_INVALID;
+  vimz_ctx* ctx = d->ctx;
+  const G16Key& K = d->key;
+  const double t_all = now_s();
+  bool chains_gpu = false;
+  { const int rcm = decider_chains_mode(ctx, &chains_gpu); if (rcm) return rcm; }
+  DeciderWitness wit;
+  { const int rcw = decider_witness(d, ivc, chains_gpu, wit); if (rcw) return rcw; }
+  const std::vector<Fe>& z = wit.z;
+  const G1Aff& cmT = wit.cmT; const uint32_t* r_low = wit.r_low; const uint64_t (*kzg_out)[12] = wit.kzg_out; const Fe &cW = wit.cW, &cE = wit.cE;
+  const double t_fold = wit.t_fold;
   std::vector<Fe> abc[3];
   host_spmv3(d->circ.b, z, abc);
   for (int q = 0; q < 3; q++) abc[q].resize(K.n, Fe::zero());
@@ -1262,9 +1372,22 @@ int vimz_decider_prove(vimz_decider* d, vimz_cf* ivc, uint64_t* public_out, uint
   memcpy(w + 76, kzg_out[0], 32); memcpy(w + 80, kzg_out[1], 32);
   memcpy(w + 84, kzg_out[0] + 4, 64); memcpy(w + 92, kzg_out[1] + 4, 64);
   for (uint32_t i = 0; i < K.n_pub; i++) { const Fe c = Fe::from_mont(z[1 + i]); memcpy(public_out + 4 * i, c.v, 32); }
-  if (seconds) { seconds[0] = t_fold - t_all; seconds[1] = t_wit - t_fold; seconds[2] = t_ntt - t_wit; seconds[3] = t_msm - t_ntt; seconds[4] = now_s() - t_all; seconds[5] = 0; }
+  if (seconds) { seconds[0] = t_fold - t_all; seconds[1] = t_wit - t_fold; seconds[2] = t_ntt - t_wit; seconds[3] = t_msm - t_ntt; seconds[4] = now_s() - t_all; seconds[5] = wit.chains_gpu_s; }
   return VIMZ_OK;
 }
+
+#ifdef VIMZ_TESTING
+// The decider's full assignment z (canonical, 4 words per wire) as vimz_decider_prove builds it for the proof `ivc` holds, with check 5's chains from the host
+// (chains_on_gpu = 0) or from the device.  Returns the byte size (copies when buf is large enough); negative: vimz_decider_prove's errors.
+int64_t vimz_testing_decider_witness(vimz_decider* d, vimz_cf* ivc, int chains_on_gpu, void* buf, size_t cap) {
+  if (!d || !ivc) return VIMZ_ERR_INVALID;
+  DeciderWitness wit;
+  { const int rc = decider_witness(d, ivc, chains_on_gpu != 0, wit); if (rc) return rc; }
+  const size_t bytes = 32 * wit.z.size();
+  if (buf && cap >= bytes) { uint64_t* o = (uint64_t*)buf; for (size_t i = 0; i < wit.z.size(); i++) { const Fe c = Fe::from_mont(wit.z[i]); memcpy(o + 4 * i, c.v, 32); } }
+  return (int64_t)bytes;
+}
+#endif
 
 // Decider::verify (reached from `verify_final_proof`, vimz/src/sonobe_backend/decider.rs:31-50, mod.rs:80): what the contract generated for this key
 // does with (steps, z_0, z_i, 25 words) — contracts/ContrastVerifier.sol:685-783 — on the host: steps >= 2, the two folded commitments, their

@@ -983,7 +983,8 @@ class Decider:
 
     def prove(self, ivc=None):
         """Decider::prove for the IVC proof `ivc` (default: the prover the decider was set up over) holds.  Returns (25 words: ints, public inputs:
-        ints, seconds dict)."""
+        ints, seconds dict).  "chains_gpu": kernel and download of check 5's chains on the device (inside the first two spans; 0 when the host makes them:
+        the light decider, or VIMZ_DECIDER_CHAINS=host — read per call; the default is gpu)."""
         ivc = self.prover if ivc is None else ivc
         n_pub = self.info()["public_inputs"]
         pub = np.zeros((n_pub, 4), dtype=np.uint64)
@@ -991,7 +992,7 @@ class Decider:
         sec = (C.c_double * 6)()
         self.ctx._chk(self.ctx.lib.vimz_decider_prove(self.h, ivc.h, _ptr(pub), _ptr(words), sec))
         ints = lambda a: [sum(int(a[i, q]) << (64 * q) for q in range(4)) for i in range(a.shape[0])]
-        return ints(words), ints(pub), {"final_fold_and_kzg": sec[0], "witness_host": sec[1], "ntt": sec[2], "msm": sec[3], "total": sec[4]}
+        return ints(words), ints(pub), {"final_fold_and_kzg": sec[0], "witness_host": sec[1], "ntt": sec[2], "msm": sec[3], "total": sec[4], "chains_gpu": sec[5]}
 
     def verify(self, steps, z0, z_i, words):
         """Decider::verify: 0 = accepted, else the bit set of RESULT_BITS."""
