@@ -35,9 +35,6 @@ namespace vz {
 // bucket in k_combine).  Results never depend on them — tests/test_gpu_ivc.py folds the same rows under other values and requires
 // the identical proof.  (The switches of rounds 1-2 whose A/B is settled — launcher thread, copied window sums, CU masks, stream
 // priorities, sub-bucket length, late folds, one producer stream — are gone; DESIGN.md §9 keeps what they measured.)
-// small_lean (0: off, the default): the fused small MSM's wide tail levels by one lane per addition instead of four — 15-20 % fewer
-// instructions per small MSM, 7-27 µs more latency: measured SLOWER in every regime (three segments 1095-1101 -> 1054-1078 -> 1029-1051
-// steps/s for lean = 0 / 1 / 2, one chain 819 -> 799 -> 770): with the GPU 98 % busy the step is still bound by its latency chains.
 // reduce_planes (0: off, the default): the shared bucket set of a table MSM reduced by bit planes (k_reduce_planes) instead of chunked running sums
 // (k_reduce) — alone on the GPU the reduce falls from 0.171 to 0.083 ms (305 k dense points, c = 15) and the whole MSM from 0.873 to 0.786 ms, but
 // every bucket is then added into half of the 14 planes: 131 k full additions instead of 32 k, a tenth of the accumulation's work on top — and inside
@@ -48,20 +45,19 @@ namespace vz {
 // the same for every such scalar (seven buckets of tens of thousands of entries each) — where the small value has 9-10 digits and empty upper windows.
 // 0 keeps the plain recoding in the binary for A/B runs and for the schedule-independence tests; the commitment is the same group element either way.
 // (rows_group, a key of the same variable, is the batch producer's: prover_internal.hpp, rows_group_wanted.)
-struct MsmTuning { int sort_blocks = 0, combine_lane_bits = -1, small_lean = 0, witness_sub = 0, ones_dense = 1, reduce_planes = 0, accum_lds_kb = 0, dense_sub = 0, signed_scalars = 1; };
+// Gone, with their code — DESIGN_LOG.md has the record: small_lean (the fused small MSM's wide tail levels by one lane per addition: fewer instructions,
+// 2-6 % fewer steps/s in every regime); accum_lds_kb (k_accum held to one or two workgroups per CU by LDS it never touches: zero-sum at two, 2 % worse at
+// one); witness_sub and dense_sub with BaseTables::sub_hint (other accumulation piece lengths: within the noise or worse; msm_shape keeps the lengths that won).
+// A key this parser does not know is ignored.  (struct MsmTuning: msm_shape.hpp)
 inline const MsmTuning& msm_tuning() {
   static const MsmTuning t = [] {
     MsmTuning r;
     if (const char* e = getenv("VIMZ_TUNE")) {
       if (const char* q = strstr(e, "sort_blocks=")) r.sort_blocks = atoi(q + 12);
       if (const char* q = strstr(e, "combine_lane_bits=")) r.combine_lane_bits = atoi(q + 18);
-      if (const char* q = strstr(e, "small_lean=")) r.small_lean = atoi(q + 11);
-      if (const char* q = strstr(e, "witness_sub=")) { const int v = atoi(q + 12); if (v >= 2 && v <= MSM_SUB) r.witness_sub = v; }
-      if (const char* q = strstr(e, "dense_sub=")) { const int v = atoi(q + 10); if (v >= 2 && v <= MSM_SUB) r.dense_sub = v; }
       if (const char* q = strstr(e, "ones_dense=")) r.ones_dense = atoi(q + 11);
       if (const char* q = strstr(e, "reduce_planes=")) r.reduce_planes = atoi(q + 14);
       if (const char* q = strstr(e, "signed_scalars=")) r.signed_scalars = atoi(q + 15) != 0;
-      if (const char* q = strstr(e, "accum_lds_kb=")) { const int v = atoi(q + 13); if (v >= 0 && v <= 160) r.accum_lds_kb = v; }
     }
     return r;
   }();
@@ -229,7 +225,6 @@ __global__ void k_scatter(const uint32_t* __restrict__ scalars, size_t n, int mo
 // Here each workgroup histograms its own contiguous chunk of scalars in LDS (all buckets fit: 24 x 1024 counters = 96 KiB),
 // a scan kernel turns the per-workgroup histograms into global bucket sizes and per-workgroup offsets, and the scatter
 // ranks its entries with LDS atomics again.  No global atomic is issued at all.
-constexpr uint32_t SORT_BLOCKS = 256;      // at most one workgroup per CU (msm_launch picks fewer for small inputs)
 constexpr uint32_t SORT_THREADS = 1024;
 
 template <class S>
@@ -624,12 +619,12 @@ __global__ void __launch_bounds__(256) k_reduce_planes(const uint32_t* __restric
 // and point chunk q (<= 1536 points): digits -> counting sort in LDS -> one thread per sub-bucket of <= 8 entries ->
 // segmented tree over a bucket's sub-buckets -> sum_b (b+1)·B_b as the sum of the 64 suffix sums (scan + tree, 12 deep) ->
 // the last workgroup of a window to finish adds the chunk results.  Depth: 8 + log2(max sub-buckets) + 12 + log2(chunks).
-// (SMALL_C, SMALL_CHUNK, SMALL_MAXQ, MSM_SMALL_MAX: msm_api.hpp)
+// (SMALL_C, SMALL_CHUNK, SMALL_MAXQ, SMALL_NBW, MSM_SMALL_MAX: msm_shape.hpp)
 // 256 threads, one wave per SIMD.  (512 threads on half-length sub-buckets — two waves per SIMD, 210 VGPRs, no spills — measured
 // SLOWER: 0.251 vs 0.187 ms at 7.7 k points, 0.167 vs 0.145 ms for one chunk: the accumulation phase does not get shorter with a second
 // wave per SIMD, and the segment tree grows.)
 constexpr uint32_t SMALL_THREADS = 256;
-constexpr uint32_t SMALL_NBW = 1u << (SMALL_C - 1), SMALL_SUB = 8 /* longest sub-bucket */, SMALL_PER_THREAD = SMALL_CHUNK / SMALL_THREADS;
+constexpr uint32_t SMALL_SUB = 8 /* longest sub-bucket */, SMALL_PER_THREAD = SMALL_CHUNK / SMALL_THREADS;
 static_assert(SMALL_CHUNK / SMALL_SUB + SMALL_NBW <= SMALL_THREADS, "one thread per sub-bucket");
 static_assert(SMALL_NBW == 64, "k_msm_small scans the buckets of a window with one wave");
 // (1536 points per workgroup: at most 1536/8 + 64 = 256 sub-buckets, one per thread; 7.6 k points -> 37 x 5 = 185 workgroups,
@@ -660,13 +655,12 @@ __device__ __forceinline__ int signed_digit(const uint32_t* s, int w) {
   return d > (1u << (C - 1)) ? (int)d - (1 << C) : (int)d;
 }
 
-template <class S, class F, int LEAN /* the option small_lean: its code is only in the instantiations that run it */>
+template <class S, class F>
 __global__ void __launch_bounds__(SMALL_THREADS) k_msm_small(const uint32_t* __restrict__ bases, const uint32_t* __restrict__ scalars, uint32_t n, int mont, int sgn,
                                                    uint32_t Q, uint32_t chunk, uint32_t* __restrict__ chunk_out /* K*Q points */,
                                                    uint32_t* __restrict__ done /* K counters, zero between launches; nullptr: k_msm_small_sum follows */,
                                                    uint32_t* __restrict__ window_sums,
                                                    const uint32_t* __restrict__ tables /* or nullptr: row w holds 2^(7w)·P_i, row length tstride */, uint32_t tstride) {
-  constexpr int lean = LEAN;      // (levels with a wave's worth of additions by one lane each instead of four: half the instructions, 3.4 µs more per level)
   __shared__ XYZZ<F> sh[SMALL_THREADS];
   __shared__ uint32_t cnt[SMALL_NBW], off[SMALL_NBW + 1], soff[SMALL_NBW + 1], cur[SMALL_NBW];
   __shared__ uint16_t list[SMALL_CHUNK];
@@ -756,18 +750,6 @@ __global__ void __launch_bounds__(SMALL_THREADS) k_msm_small(const uint32_t* __r
     for (uint32_t wv = 0; wv < SMALL_THREADS / 64; wv++) { before += wv < (t >> 6) ? wcnt[wv] : 0u; total += wcnt[wv]; }
     if (act) list[before + (uint32_t)__popcll(bal & ((1ull << (t & 63)) - 1ull))] = (uint16_t)t;
     __syncthreads();
-    if (lean && total >= 48) {
-      // one lane per addition, the pairs packed into the first waves: a wave's 64 additions cost what 16 cost four lanes each
-      const uint32_t wave0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(t & ~63u));
-      XYZZ<F> a; uint32_t ia = 0; bool mine = false;
-      if (wave0 < total) {
-        mine = t < total;
-        if (mine) { ia = list[t]; a = sh[ia]; add_full(a, sh[ia + d]); }
-      }
-      __syncthreads();
-      if (mine) sh[ia] = a;
-      __syncthreads();
-    } else
     for (uint32_t base = 0; base < total; base += 64)
       quad_level<F>(sh, min(64u, total - base), [&](uint32_t e) { return (uint32_t)list[base + e]; }, [&](uint32_t e) { return (uint32_t)list[base + e] + d; });
   }
@@ -801,17 +783,9 @@ __global__ void __launch_bounds__(SMALL_THREADS) k_msm_small(const uint32_t* __r
         sh[t] = load_xyzz<F>(chunk_out, ((size_t)w * Q + loaded + sl - slot0) * SMALL_NBW + b);
       }
       __syncthreads();
-      if (lean) {
-        // slots (0 += 1) and (2 += 3) side by side on waves 0 and 2, one lane per bucket; then 0 += 2 on wave 0
-        if ((sl == 0 && m >= 2) || (sl == 2 && m == 4)) { XYZZ<F> a = sh[t]; add_full(a, sh[t + SMALL_NBW]); sh[t] = a; }      // (a wave reads and writes its own slot pair only)
-        __syncthreads();
-        if (sl == 0 && m >= 3) { XYZZ<F> a = sh[t]; add_full(a, sh[t + 2 * SMALL_NBW]); sh[t] = a; }
-        __syncthreads();
-      } else {
       if (m >= 2) quad_level<F>(sh, SMALL_NBW, [](uint32_t e) { return e; }, [](uint32_t e) { return e + SMALL_NBW; });
       if (m == 4) quad_level<F>(sh, SMALL_NBW, [](uint32_t e) { return e + 2 * SMALL_NBW; }, [](uint32_t e) { return e + 3 * SMALL_NBW; });
       if (m >= 3) quad_level<F>(sh, SMALL_NBW, [](uint32_t e) { return e; }, [](uint32_t e) { return e + 2 * SMALL_NBW; });
-      }
       loaded += k;
     }
     if (t == 0) __hip_atomic_store(&done[w], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -820,15 +794,6 @@ __global__ void __launch_bounds__(SMALL_THREADS) k_msm_small(const uint32_t* __r
     __syncthreads();
   }
   // The rest is twelve levels of at most 64 dependent additions: four lanes per addition (ec_mem.hpp: quad_level), all four waves busy.
-  if (lean >= 2) {      // (experiment: the six scan levels by one lane per bucket on wave 0: 19 k fewer instructions per window, 20 µs more latency)
-    for (uint32_t d = 1; d < SMALL_NBW; d <<= 1) {
-      XYZZ<F> a; const bool mine = t < SMALL_NBW - d;
-      if (t < 64) { if (mine) { a = sh[t]; add_full(a, sh[t + d]); } }
-      __syncthreads();
-      if (mine) sh[t] = a;
-      __syncthreads();
-    }
-  } else
   for (uint32_t d = 1; d < SMALL_NBW; d <<= 1)      // inclusive suffix sums of the buckets
     quad_level<F>(sh, SMALL_NBW - d, [](uint32_t e) { return e; }, [d](uint32_t e) { return e + d; });
   for (uint32_t d = SMALL_NBW / 2; d > 0; d >>= 1)  // sum_b (b+1)·B_b = sum of the suffix sums
@@ -859,7 +824,7 @@ __global__ void __launch_bounds__(64) k_msm_small_sum(const uint32_t* __restrict
 // of n·37 points — no digit sort, no bucket accumulation chains, no weighted bucket reduction (twelve dependent additions).  Depth:
 // three mixed additions per thread (four points each), the 256-leaf tree of a workgroup (nine four-lane rounds), the tree over a
 // window's ≤ 32 workgroup sums by the last workgroup of the window to arrive; the host adds the 37 window sums as before.
-constexpr uint32_t FIXED_PER_THREAD = 4, FIXED_CHUNK = 256 * FIXED_PER_THREAD, FIXED_MAXQ = 64;
+constexpr uint32_t FIXED_MAXQ = 64;      // (FIXED_PER_THREAD, FIXED_CHUNK: msm_shape.hpp)
 static_assert(MSM_SMALL_MAX <= (size_t)FIXED_CHUNK * FIXED_MAXQ, "a window's workgroup sums fit one tree");
 
 template <class F>
@@ -951,9 +916,6 @@ __global__ void __launch_bounds__(256) k_msm_fixed(const uint32_t* __restrict__ 
   if (t == 0) { store_xyzz(window_sums, w, sh[0]); __hip_atomic_store(&done[w], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 }
 
-// ---- host driver ---------------------------------------------------------------------------------
-
-
 // ---- window tables: one bucket set for all windows ---------------------------------------------------------------------
 // With T_j[i] = 2^(c·j)·P_i precomputed (the commitment key is fixed for the whole proof and HBM is plentiful), digit j of
 // scalar i is an entry (T_j[i], bucket |d|): every window shares ONE set of 2^(c-1) buckets, so c can be large (fewer
@@ -989,207 +951,194 @@ hipError_t build_tables(hipStream_t stream, const uint32_t* d_bases, size_t n, i
   return hipGetLastError();
 }
 
-// Enqueue the whole pipeline on `stream` and the copy of the K window sums into `pinned_dst` (host-pinned,
-// K * XYZZ_WORDS words).  Does not synchronise: the caller waits on the stream (or an event recorded after this call)
-// and then calls msm_finish.  `ws` must not be used by another stream concurrently.
+// ---- host driver ---------------------------------------------------------------------------------
+// Enqueue the whole pipeline on `stream`; the window sums go straight into `pinned_dst` (host-pinned memory the device can write, msm_sums_out(plan)
+// points: the copy that used to follow — a launch and a dependent hop between the last kernel and the host's wake-up — is gone).  Does not synchronise:
+// the caller waits on the stream (or an event recorded after this call) and then calls msm_finish.  `ws` must not be used by another stream concurrently.
 // The rows of a group (msm_launch_rows; rg == nullptr: msm_launch, one vector): how many, where row r's scalars and sums lie, what the workspace is sized for,
 // the caller's further unit sums.  A shape the grouped chain does not cover returns hipErrorNotSupported BEFORE anything is launched or reserved.
-struct MsmRowGroup { uint32_t G; size_t scalar_row_stride /* scalars */, pinned_row_stride /* bytes */; const OnesDesc* extra; uint32_t n_extra; uint32_t max_rows; size_t* row_bytes_out /* only report a row's device bytes */; };
+struct MsmRowGroup { uint32_t G; size_t scalar_row_stride /* scalars */, pinned_row_stride /* bytes */; const OnesDesc* extra; uint32_t n_extra; uint32_t max_rows; };
+// what the three launchers below share: the call's arguments; every size comes from a finished MsmShape (msm_shape.hpp)
+struct MsmCall {
+  hipStream_t stream; MsmWorkspace& ws; const uint32_t* d_bases; const uint32_t* d_scalars; size_t n; int scalars_mont, sgn, split_ones;
+  uint32_t* wsum /* the caller's pinned buffer */; hipEvent_t* ev; const BaseTables* tb; const MsmRowGroup* rg;
+};
+static inline MsmTableDesc msm_table_desc(const BaseTables* tb) {
+  MsmTableDesc t;
+  if (tb && tb->d) { t.present = true; t.c = tb->c; t.K = tb->K; t.own = tb->own; t.mult = tb->mult != nullptr; t.n_total = tb->n_total; }
+  return t;
+}
+static inline bool msm_no_small() {      // (tables of the fused path are then ignored, not an error)
+  static const bool no_small = getenv("VIMZ_DEBUG_NO_SMALL_MSM") != nullptr;
+  return no_small;
+}
+#define VZ_EV(i) do { if (a.ev) VZ_HIP_CHECK(hipEventRecord(a.ev[i], a.stream)); } while (0)
+
+// every multiple of the key slice resident: the digits select their points
+template <class C>
+static hipError_t launch_fixed(const MsmCall& a, const MsmShape& sh) {
+  typedef typename C::Coord F;
+  typedef typename C::Scalar S;
+  VZ_HIP_CHECK(a.ws.reserve_small());
+  uint32_t* done = reinterpret_cast<uint32_t*>(a.ws.small_buf);
+  for (int i = 0; i < 4; i++) VZ_EV(i);
+  hipLaunchKernelGGL((k_msm_fixed<S, F>), dim3(sh.Qf, sh.plan.K), dim3(256), 0, a.stream, a.tb->mult + (size_t)AFFINE_WORDS * SMALL_NBW * a.tb->offset, (uint32_t)a.tb->n_total, a.d_scalars,
+                     (uint32_t)a.n, a.scalars_mont, a.sgn, sh.Qf, done + 128, done, a.wsum);
+  for (int i = 4; i < 7; i++) VZ_EV(i);
+  return hipGetLastError();
+}
+
+// the fused single launch; with tables made for it (plan.tabled == 2) window w reads row w of them
+template <class C>
+static hipError_t launch_small(const MsmCall& a, const MsmShape& sh) {
+  typedef typename C::Coord F;
+  typedef typename C::Scalar S;
+  VZ_HIP_CHECK(a.ws.reserve_small());
+  uint32_t* done = reinterpret_cast<uint32_t*>(a.ws.small_buf);
+  uint32_t* chunk_out = done + 128;
+  const bool small_tb = sh.plan.tabled == 2;
+  for (int i = 0; i < 4; i++) VZ_EV(i);
+  static const bool sum_kernel = getenv("VIMZ_DEBUG_SMALL_SUM_KERNEL") != nullptr;
+  hipLaunchKernelGGL((k_msm_small<S, F>), dim3(sh.plan.K, sh.Q), dim3(SMALL_THREADS), 0, a.stream, a.d_bases, a.d_scalars, (uint32_t)a.n, a.scalars_mont, a.sgn, sh.Q, sh.chunk, chunk_out,
+                     sum_kernel ? (uint32_t*)nullptr : done, a.wsum,
+                     small_tb ? a.tb->d + (size_t)AFFINE_WORDS * a.tb->offset : (const uint32_t*)nullptr, small_tb ? (uint32_t)a.tb->n_total : 0u);
+  if (sh.Q > 1 && sum_kernel) hipLaunchKernelGGL(k_msm_small_sum<F>, dim3(sh.plan.K), dim3(64), 0, a.stream, chunk_out, sh.Q, a.wsum);
+  for (int i = 4; i < 7; i++) VZ_EV(i);
+  return hipGetLastError();
+}
+
+// the >64 KiB dynamic-LDS opt-in of the LDS sort is per device and per kernel instantiation; contexts fold from several host threads
+template <class S>
+static hipError_t lds_sort_opt_in() {
+  static std::mutex attr_mu;
+  static uint64_t attr_devices = 0;
+  int dev = 0;
+  VZ_HIP_CHECK(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> g(attr_mu);
+  if (!((attr_devices >> (dev & 63)) & 1ull)) {
+    VZ_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_hist_lds<S>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    VZ_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scatter_lds<S>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    attr_devices |= 1ull << (dev & 63);
+  }
+  return hipSuccess;
+}
+
+// events 0..3: digits -> histogram -> scan -> entries in bucket order (ws.sorted), by the LDS counting sort or, where the counters do not fit LDS, with global atomics
+template <class S>
+static hipError_t launch_sort(const MsmCall& a, const MsmShape& sh, const MsmRowStrides& rs, uint32_t G) {
+  const MsmPlan& pl = sh.plan;
+  MsmWorkspace& ws = a.ws;
+  VZ_EV(0);
+  if (sh.lds_sort) {
+    VZ_HIP_CHECK(ws.reserve_block_hist((size_t)SORT_BLOCKS * pl.nb));
+    VZ_HIP_CHECK(lds_sort_opt_in<S>());
+    hipLaunchKernelGGL(k_hist_lds<S>, dim3(sh.sort_blocks, G), dim3(SORT_THREADS), pl.nb * 4, a.stream, a.d_scalars, a.n, a.scalars_mont, a.split_ones, a.sgn, pl.c, pl.K, sh.bstride, pl.nb,
+                       ws.block_hist, rs);
+    VZ_EV(1);
+    // per-workgroup histograms -> prefixes and totals, and (last workgroup) the scan: one launch
+    hipLaunchKernelGGL(k_prefix_scan<0>, dim3((pl.nb + 1023) / 1024, G), dim3(1024), 0, a.stream, ws.block_hist, pl.nb, ws.counts, sh.sort_blocks, ws.heavy, ws.bucket_off, ws.sub_off,
+                       ws.totals, sh.sub, sh.heavy_min, MSM_HEAVY_CAP, rs);
+    VZ_EV(2);
+    hipLaunchKernelGGL(k_scatter_lds<S>, dim3(sh.sort_blocks, G), dim3(SORT_THREADS), pl.nb * 4, a.stream, a.d_scalars, a.n, a.scalars_mont, a.split_ones, a.sgn, pl.c, pl.K, sh.bstride, pl.nb,
+                       sh.pstride, ws.bucket_off, ws.block_hist, ws.sorted, rs);
+  } else {      // (one row only: msm_shape)
+    const unsigned gs = (unsigned)std::min<size_t>((a.n + 255) / 256, 256 * 16);
+    // (the LDS sort writes every counter itself and needs no cursors; each fill is a launch of its own)
+    VZ_HIP_CHECK(hipMemsetAsync(ws.counts, 0, 4 * (size_t)pl.nb, a.stream));
+    VZ_HIP_CHECK(hipMemsetAsync(ws.cursor, 0, 4 * (size_t)pl.nb, a.stream));
+    VZ_HIP_CHECK(hipMemsetAsync(ws.heavy, 0, 4, a.stream));
+    hipLaunchKernelGGL(k_hist<S>, dim3(gs), dim3(256), 0, a.stream, a.d_scalars, a.n, a.scalars_mont, a.split_ones, a.sgn, pl.c, pl.K, sh.bstride, ws.counts);
+    VZ_EV(1);
+    hipLaunchKernelGGL(k_scan<MSM_SUB>, dim3(1), dim3(1024), 0, a.stream, ws.counts, pl.nb, ws.bucket_off, ws.sub_off, ws.totals, sh.sub, ws.heavy, sh.heavy_min, MSM_HEAVY_CAP);
+    VZ_EV(2);
+    hipLaunchKernelGGL(k_scatter<S>, dim3(gs), dim3(256), 0, a.stream, a.d_scalars, a.n, a.scalars_mont, a.split_ones, a.sgn, pl.c, pl.K, sh.bstride, sh.pstride,
+                       ws.bucket_off, ws.cursor, ws.sorted);
+  }
+  VZ_EV(3);
+  return hipSuccess;
+}
+
+// the unit sums of a split MSM, after the reduce's sh.kout sums: a group's rows' — and the caller's own — in two launches; one vector's by three
+template <class C>
+static hipError_t launch_unit_sums(const MsmCall& a, const MsmShape& sh, uint32_t G) {
+  typedef typename C::Coord F;
+  typedef typename C::Scalar S;
+  const MsmRowGroup* rg = a.rg;
+  if (rg) {
+    OnesDesc ds[2 * MSM_ROWS_MAX];
+    for (uint32_t r = 0; r < G; r++) ds[r] = OnesDesc{a.d_scalars + 8 * r * rg->scalar_row_stride, a.d_bases, a.wsum + r * (rg->pinned_row_stride / 4) + (size_t)XYZZ_WORDS * sh.kout, a.n};
+    for (uint32_t e = 0; e < rg->n_extra; e++) ds[G + e] = rg->extra[e];
+    return ones_launch_rows<C>(a.stream, a.ws, ds, G + rg->n_extra, a.scalars_mont);
+  }
+  uint32_t* lvl0 = reinterpret_cast<uint32_t*>(a.ws.ones_partial);
+  if (msm_tuning().ones_dense) hipLaunchKernelGGL((k_ones_dense<S, F>), dim3(ONES_THREADS / 256), dim3(256), 0, a.stream, a.d_scalars, a.d_bases, a.n, a.scalars_mont, lvl0);
+  else hipLaunchKernelGGL((k_ones_partial<S, F>), dim3(ONES_THREADS / 256), dim3(256), 0, a.stream, a.d_scalars, a.d_bases, a.n, a.scalars_mont, lvl0);
+  uint32_t* lvl1 = lvl0 + (size_t)XYZZ_WORDS * ONES_THREADS;
+  hipLaunchKernelGGL(k_tree256<F>, dim3(ONES_THREADS / 256), dim3(256), 0, a.stream, lvl0, ONES_THREADS, lvl1);
+  hipLaunchKernelGGL(k_tree256<F>, dim3(1), dim3(256), 0, a.stream, lvl1, ONES_THREADS / 256, a.wsum + (size_t)XYZZ_WORDS * sh.kout);
+  return hipSuccess;
+}
+
+// the general pipeline: sort, accumulate, combine, reduce (events 0..6), unit sums
+template <class C>
+static hipError_t launch_large(const MsmCall& a, const MsmShape& sh) {
+  typedef typename C::Coord F;
+  typedef typename C::Scalar S;
+  const MsmPlan& pl = sh.plan;
+  const MsmRowGroup* rg = a.rg;
+  MsmWorkspace& ws = a.ws;
+  const uint32_t G = rg ? rg->G : 1u;
+  VZ_HIP_CHECK(ws.reserve(pl.nb, sh.entries, sh.max_subs, rg ? std::max<size_t>(G, rg->max_rows) : 1));
+  // row slices: strides of this call's sizes (the tickets' arrays — totals, heavy_done — keep fixed strides, so every ticket stays where it was zeroed)
+  MsmRowStrides rs;
+  if (G > 1) {
+    rs.scalars = 8 * rg->scalar_row_stride; rs.block_hist = (size_t)SORT_BLOCKS * pl.nb; rs.sorted = sh.entries; rs.partial = (size_t)XYZZ_WORDS * sh.max_subs;
+    rs.heavy_scratch = MsmWorkspace::HEAVY_SCRATCH_WORDS; rs.out = rg->pinned_row_stride / 4;
+    rs.counts = pl.nb; rs.offs = pl.nb + 1; rs.totals = MSM_TOTALS_WORDS; rs.heavy = MSM_HEAVY_CAP + 1; rs.heavy_done = MSM_HEAVY_DONE_WORDS;
+  }
+  VZ_HIP_CHECK(launch_sort<S>(a, sh, rs, G));
+  uint32_t* partial = reinterpret_cast<uint32_t*>(ws.partial);
+  hipLaunchKernelGGL(k_accum<F>, dim3((unsigned)((sh.max_subs + 255) / 256), G), dim3(256), 0, a.stream, a.d_bases, ws.sorted, ws.bucket_off, ws.sub_off, pl.nb, ws.totals, partial, sh.sub, rs);
+  VZ_EV(4);
+  const unsigned per_wg = 256u >> sh.lane_bits, nbn = (pl.nb + per_wg - 1) / per_wg;
+  hipLaunchKernelGGL(k_combine<F>, dim3(nbn + COMBINE_HEAVY_BLOCKS + COMBINE_SPLIT_BLOCKS, G), dim3(256), 0, a.stream, partial, ws.sub_off, pl.nb, nbn,
+                     (const uint32_t*)ws.heavy, MSM_HEAVY_CAP, ws.heavy_scratch, sh.lane_bits, sh.heavy_min, ws.heavy_done, rs);
+  VZ_EV(5);      // (stage 2 of the very heavy buckets: the last of a bucket's workgroups, inside k_combine)
+  // sh.kout sums: planes + two plain halves; (R_v, S_v) per virtual window of a shared bucket set; or one per window
+  if (sh.planes) {
+    hipLaunchKernelGGL(k_reduce_planes<F>, dim3((sh.Pl + 2) * sh.Gp), dim3(256), 0, a.stream, (const uint32_t*)partial, (const uint32_t*)ws.counts, (const uint32_t*)ws.sub_off, pl.nbw, sh.Pl, sh.Gp,
+                       pl.nbw / (512u * sh.Gp), ws.plane_scratch, ws.totals + 3, a.wsum);
+  } else if (sh.shared) {
+    hipLaunchKernelGGL(k_reduce<F>, dim3(sh.V, G), dim3(sh.vw < 256 ? sh.vw : 256), 0, a.stream, (const uint32_t*)partial, (const uint32_t*)ws.counts, (const uint32_t*)ws.sub_off, sh.vw, a.wsum,
+                       a.wsum + (size_t)XYZZ_WORDS * sh.V, rs);
+  } else
+    hipLaunchKernelGGL(k_reduce<F>, dim3(pl.K, G), dim3(pl.nbw < 256 ? pl.nbw : 256), 0, a.stream, (const uint32_t*)partial, (const uint32_t*)ws.counts, (const uint32_t*)ws.sub_off, pl.nbw, a.wsum,
+                       (uint32_t*)nullptr, rs);
+  VZ_EV(6);
+  if (a.split_ones) VZ_HIP_CHECK(launch_unit_sums<C>(a, sh, G));
+  return hipGetLastError();
+}
+#undef VZ_EV
+
 template <class C>
 static hipError_t msm_launch_impl(hipStream_t stream, MsmWorkspace& ws, const uint32_t* d_bases, const uint32_t* d_scalars, size_t n,
                                   int scalars_mont, int c_override, void* pinned_dst, MsmPlan* plan_out, hipEvent_t* ev, int split_ones,
                                   const BaseTables* tb, const MsmRowGroup* rg) {
-  typedef typename C::Coord F;
-  typedef typename C::Scalar S;
-  if (n == 0 || n >= (1u << 31)) return hipErrorInvalidValue;
-  const uint32_t G = rg ? rg->G : 1u;
-  if (rg && !rg->row_bytes_out && (G == 0 || G > MSM_ROWS_MAX || rg->n_extra > MSM_ROWS_MAX || (split_ones == 0 && rg->n_extra))) return hipErrorInvalidValue;
-  const int sgn = msm_tuning().signed_scalars;
-  // The window sums go straight into the caller's pinned buffer (host memory the device can write): the copy that used to follow —
-  // a launch and a dependent hop between the last kernel and the host's wake-up — is gone.
-  constexpr bool direct = true;
-  // tables made for the fused small path (window SMALL_C): its window sums then only need adding — no Horner on the host
-  static const bool no_small = getenv("VIMZ_DEBUG_NO_SMALL_MSM") != nullptr;
-  const bool small_fmt = tb && tb->d && tb->c == SMALL_C;             // (ignored, not an error, when the fused path is switched off)
-  const bool small_tb = small_fmt && !no_small && c_override <= 0;
-  bool tabled = tb && tb->d && !small_fmt && c_override <= 0;
-  // tables with per-window bucket sets only fit the window this size would get anyway; otherwise they are not used
-  if (tabled && tb->own && tb->c != msm_plan(n, S::Params::BITS, 0).c) tabled = false;
-  const bool own = tabled && tb->own;
-  if (small_tb && (n > MSM_SMALL_MAX || tb->K != (S::Params::BITS + SMALL_C) / SMALL_C)) return hipErrorInvalidValue;
-  if (!no_small && !tabled && c_override <= 0 && n <= MSM_SMALL_MAX) {      // fused single-launch path
-    if (rg) return hipErrorNotSupported;
-    MsmPlan ps; ps.c = SMALL_C; ps.K = (S::Params::BITS + SMALL_C) / SMALL_C; ps.nbw = SMALL_NBW; ps.nb = SMALL_NBW * (uint32_t)ps.K; ps.split_ones = 0; ps.tabled = small_tb ? 2 : 0;
-    *plan_out = ps;
-    VZ_HIP_CHECK(ws.reserve_small());
-    const uint32_t Q = (uint32_t)((n + SMALL_CHUNK - 1) / SMALL_CHUNK), chunk = (uint32_t)((n + Q - 1) / Q);
-    uint32_t* done = reinterpret_cast<uint32_t*>(ws.small_buf);
-    uint32_t* chunk_out = done + 128;
-    if (small_tb && tb->mult) {      // every multiple resident: the digits select their points (k_msm_fixed)
-      const uint32_t Qf = (uint32_t)((n + FIXED_CHUNK - 1) / FIXED_CHUNK);
-      if (ev) for (int i = 0; i < 4; i++) VZ_HIP_CHECK(hipEventRecord(ev[i], stream));
-      hipLaunchKernelGGL((k_msm_fixed<S, F>), dim3(Qf, ps.K), dim3(256), 0, stream, tb->mult + (size_t)AFFINE_WORDS * SMALL_NBW * tb->offset, (uint32_t)tb->n_total, d_scalars, (uint32_t)n,
-                         scalars_mont, sgn, Qf, chunk_out, done, direct ? reinterpret_cast<uint32_t*>(pinned_dst) : reinterpret_cast<uint32_t*>(ws.window_sums));
-      if (ev) for (int i = 4; i < 7; i++) VZ_HIP_CHECK(hipEventRecord(ev[i], stream));
-      VZ_HIP_CHECK(hipGetLastError());
-      if (!direct) VZ_HIP_CHECK(hipMemcpyAsync(pinned_dst, ws.window_sums, 4 * (size_t)XYZZ_WORDS * ps.K, hipMemcpyDeviceToHost, stream));
-      return hipSuccess;
-    }
-    if (ev) for (int i = 0; i < 4; i++) VZ_HIP_CHECK(hipEventRecord(ev[i], stream));
-    static const bool sum_kernel = getenv("VIMZ_DEBUG_SMALL_SUM_KERNEL") != nullptr;
-#define VZ_SMALL(LEAN) hipLaunchKernelGGL((k_msm_small<S, F, LEAN>), dim3(ps.K, Q), dim3(SMALL_THREADS), 0, stream, d_bases, d_scalars, (uint32_t)n, scalars_mont, sgn, Q, chunk, chunk_out, \
-                       sum_kernel ? (uint32_t*)nullptr : done, direct ? reinterpret_cast<uint32_t*>(pinned_dst) : reinterpret_cast<uint32_t*>(ws.window_sums), \
-                       small_tb ? tb->d + (size_t)AFFINE_WORDS * tb->offset : (const uint32_t*)nullptr, small_tb ? (uint32_t)tb->n_total : 0u)
-    switch (msm_tuning().small_lean) { case 0: VZ_SMALL(0); break; case 1: VZ_SMALL(1); break; default: VZ_SMALL(2); break; }
-#undef VZ_SMALL
-    if (Q > 1 && sum_kernel) hipLaunchKernelGGL(k_msm_small_sum<F>, dim3(ps.K), dim3(64), 0, stream, chunk_out, Q, direct ? reinterpret_cast<uint32_t*>(pinned_dst) : reinterpret_cast<uint32_t*>(ws.window_sums));
-    if (ev) for (int i = 4; i < 7; i++) VZ_HIP_CHECK(hipEventRecord(ev[i], stream));
-    VZ_HIP_CHECK(hipGetLastError());
-    if (!direct) VZ_HIP_CHECK(hipMemcpyAsync(pinned_dst, ws.window_sums, 4 * (size_t)XYZZ_WORDS * ps.K, hipMemcpyDeviceToHost, stream));
-    return hipSuccess;
-  }
-  MsmPlan pl = msm_plan(n, S::Params::BITS, tabled ? tb->c : c_override);
-  if (tabled) {            // one bucket set shared by all windows — or (own) the usual ones, whose sums then need no Horner
-    if (tb->K != pl.K || pl.nbw < 256 || (size_t)tb->K * tb->n_total >= (1u << 31)) return hipErrorInvalidValue;
-    if (!own && 2 * (pl.nbw / std::min<uint32_t>(pl.nbw, MSM_VWIN)) + 1 > (uint32_t)MSM_MAX_WINDOWS) return hipErrorInvalidValue;
-    if (own) pl.tabled = 3; else { pl.nb = pl.nbw; pl.tabled = 1; }
-    d_bases = tb->d + (size_t)AFFINE_WORDS * tb->offset;
-  }
-  if (pl.K + 1 > MSM_MAX_WINDOWS || pl.c > 16 || pl.c < 2) return hipErrorInvalidValue;
-  pl.split_ones = split_ones;
-  // shared bucket set: as virtual windows (k_reduce), or — VIMZ_TUNE=reduce_planes=1 — by bit planes (k_reduce_planes) where the plane workgroups' partial sums fit one tree
-  const bool no_planes = !msm_tuning().reduce_planes;
-  uint32_t Pl = 0; while ((1u << Pl) < pl.nbw) Pl++;
-  uint32_t Gp = std::min<uint32_t>(16u, pl.nbw / 1024u);
-  while (Gp > 1 && (Pl + 2) * Gp > 256) Gp >>= 1;
-  const bool planes = tabled && !own && !no_planes && pl.nbw >= 1024 && (1u << Pl) == pl.nbw && (Pl + 2) * Gp <= 256 && (int)Pl + 2 + 1 <= MSM_MAX_WINDOWS;
-  if (planes) pl.tabled = 4;
-  const bool lds_sort = (size_t)pl.nb * 4 <= 144 * 1024;      // all buckets' counters fit in one workgroup's LDS at the default window (24 x 1024 x 4 B = 96 KiB): contention-free sort
-  if (rg && (planes || own || !lds_sort)) return hipErrorNotSupported;
+  MsmShape sh;
+  MsmGroupDesc gd;
+  if (rg) { gd.grouped = true; gd.G = rg->G; gd.n_extra = rg->n_extra; }
+  const int rc = msm_shape(sh, n, C::Scalar::Params::BITS, c_override, split_ones, msm_table_desc(tb), gd, msm_tuning(), msm_no_small());
+  if (rc != MSM_SHAPE_OK) return rc == MSM_SHAPE_NOT_SUPPORTED ? hipErrorNotSupported : hipErrorInvalidValue;      // (nothing reserved, nothing launched)
   // (ONE assignment, every field final: the plan object is often shared — the producer's issuer thread launches row r + k while the folding thread
   //  finishes row r with the same plan, msm_finish — and a launch must never be seen half-described)
-  *plan_out = pl;
-  const size_t entries = (size_t)pl.K * n;
-  // small MSMs are latency-bound (one dependent addition ~ 6-10 us): shorter chains per thread, more threads
-  // (a witness commitment — split_ones — of an HD-sized circuit is a few 10^5 entries spread thinly over the buckets: one thread per bucket and a
-  //  chain of a dozen additions each on a quarter of the GPU; pieces of 8 give twice the threads half the chain: 1 045-1 061 -> 1 088-1 097 steps/s at
-  //  contrast HD, one chain 808 -> 823; at 4K the buckets are three times as full and the long pieces stay (558 against 542).  VIMZ_TUNE=witness_sub=N pins it.)
-  const int wsub = msm_tuning().witness_sub;
-  // (longer pieces for the dense MSM(T) — 24 / 32 entries, half the partials for k_combine — measured within the noise at 256 rows and
-  //  worse in the 20-row window and on one chain: 842 against 876, 786 against 812)
-  const int dsub = tb && tb->sub_hint > 0 ? tb->sub_hint : msm_tuning().dense_sub;      // (a caller that knows its vector is sparse — ivc.hip's boolean-row form — asks for shorter pieces)
-  const uint32_t sub = n < (1u << 15) ? 8u : split_ones ? (uint32_t)(wsub > 0 ? wsub : n < (1u << 19) ? 8 : MSM_SUB) : (uint32_t)(dsub >= 2 && dsub <= (int)MSM_SUB ? dsub : MSM_SUB);   // MSM_SUB for everything large
-  const size_t max_subs = entries / sub + pl.nb + 1;
-  if (rg && rg->row_bytes_out) { *rg->row_bytes_out = MsmWorkspace::row_bytes(pl.nb, entries, max_subs, (size_t)SORT_BLOCKS * pl.nb); return hipSuccess; }
-  VZ_HIP_CHECK(ws.reserve(pl.nb, entries, max_subs, rg ? std::max<size_t>(G, rg->max_rows) : 1));
-  // row slices: strides of this call's sizes (the tickets' arrays — totals, heavy_done — keep fixed strides, so every ticket stays where it was zeroed)
-  MsmRowStrides rs;
-  if (G > 1) {
-    rs.scalars = 8 * rg->scalar_row_stride; rs.block_hist = (size_t)SORT_BLOCKS * pl.nb; rs.sorted = entries; rs.partial = (size_t)XYZZ_WORDS * max_subs;
-    rs.heavy_scratch = MsmWorkspace::HEAVY_SCRATCH_WORDS; rs.out = rg->pinned_row_stride / 4;
-    rs.counts = pl.nb; rs.offs = pl.nb + 1; rs.totals = MsmWorkspace::TOTALS_WORDS; rs.heavy = MsmWorkspace::HEAVY_CAP + 1; rs.heavy_done = MsmWorkspace::HEAVY_DONE_WORDS;
+  *plan_out = sh.plan;
+  if (sh.path == MSM_PATH_LARGE && sh.plan.tabled) d_bases = tb->d + (size_t)AFFINE_WORDS * tb->offset;      // the general pipeline over window tables
+  const MsmCall a{stream, ws, d_bases, d_scalars, n, scalars_mont, msm_tuning().signed_scalars, split_ones, reinterpret_cast<uint32_t*>(pinned_dst), ev, tb, rg};
+  switch (sh.path) {
+    case MSM_PATH_FIXED: return launch_fixed<C>(a, sh);
+    case MSM_PATH_SMALL: return launch_small<C>(a, sh);
+    default: return launch_large<C>(a, sh);
   }
-  const int TB = 256;
-#define VZ_EV(i) do { if (ev) VZ_HIP_CHECK(hipEventRecord(ev[i], stream)); } while (0)
-  VZ_EV(0);
-  const unsigned gs = (unsigned)std::min<size_t>((n + TB - 1) / TB, 256 * 16);
-  if (!lds_sort) {      // (the LDS sort writes every counter itself and needs no cursors; each fill is a launch of its own)
-    VZ_HIP_CHECK(hipMemsetAsync(ws.counts, 0, 4 * (size_t)pl.nb, stream));
-    VZ_HIP_CHECK(hipMemsetAsync(ws.cursor, 0, 4 * (size_t)pl.nb, stream));
-    VZ_HIP_CHECK(hipMemsetAsync(ws.heavy, 0, 4, stream));
-  }
-  const int sort_blocks_env = msm_tuning().sort_blocks;
-  // every sort workgroup zeroes, writes out and later re-reads all nb counters (96 KiB at the default window): with one workgroup
-  // per CU at 305 k points each handled 1.2 k scalars for 24.5 k counters, and k_block_prefix walked 256 rows — fixed costs.
-  // About 4 k scalars per workgroup (75 workgroups here) measured best: one proof 384 -> 394 steps/s, three 599 -> 614.
-  const uint32_t sort_blocks = sort_blocks_env > 0 && sort_blocks_env <= (int)SORT_BLOCKS ? (uint32_t)sort_blocks_env
-                                                                                           : (uint32_t)std::min<size_t>(SORT_BLOCKS, std::max<size_t>(32, n / 4096));
-  const uint32_t bstride = tabled && !own ? 0u : pl.nbw, pstride = tabled ? (uint32_t)tb->n_total : 0u;
-  if (lds_sort) {
-    VZ_HIP_CHECK(ws.reserve_block_hist((size_t)SORT_BLOCKS * pl.nb));
-    {   // the >64 KiB dynamic-LDS opt-in is per device and per kernel instantiation; contexts fold from several host threads
-      static std::mutex attr_mu;
-      static uint64_t attr_devices = 0;
-      int dev = 0;
-      VZ_HIP_CHECK(hipGetDevice(&dev));
-      std::lock_guard<std::mutex> g(attr_mu);
-      if (!((attr_devices >> (dev & 63)) & 1ull)) {
-        VZ_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_hist_lds<S>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        VZ_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scatter_lds<S>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_devices |= 1ull << (dev & 63);
-      }
-    }
-    hipLaunchKernelGGL(k_hist_lds<S>, dim3(sort_blocks, G), dim3(SORT_THREADS), pl.nb * 4, stream, d_scalars, n, scalars_mont, split_ones, sgn, pl.c, pl.K, bstride, pl.nb, ws.block_hist, rs);
-  } else {
-    hipLaunchKernelGGL(k_hist<S>, dim3(gs), dim3(TB), 0, stream, d_scalars, n, scalars_mont, split_ones, sgn, pl.c, pl.K, bstride, ws.counts);
-  }
-  VZ_EV(1);
-  // lanes per ordinary bucket in k_combine, from the mean number of partials per bucket (upper bound: every digit non-zero): two
-  // lanes up to ~24 partials (measured at 312 k dense points, 19 per bucket: 16 lanes 0.28 ms, 8: 0.155, 4: 0.137, 2: 0.117;
-  // one lane and a heavy list of every bucket: 3.5 ms); buckets above 16 partials per lane go to the heavy list
-  // (a witness — split_ones — has far fewer entries than its upper bound: an eighth is assumed, which gives its buckets two lanes where
-  //  the bound gave four: k_combine 31.4 -> 29.1 M instructions per step)
-  const size_t mean_parts = (split_ones ? entries / 8 : entries) / sub / pl.nb + 1;
-  const int lane_bits_env = msm_tuning().combine_lane_bits;
-  const uint32_t lane_bits = lane_bits_env >= 0 ? (uint32_t)lane_bits_env : mean_parts > 96 ? 4u : mean_parts > 48 ? 3u : mean_parts > 24 ? 2u : 1u;
-  const uint32_t heavy_min = 16u << lane_bits;
-  if (lds_sort)      // per-workgroup histograms -> prefixes and totals, and (last workgroup) the scan: one launch
-    hipLaunchKernelGGL(k_prefix_scan<0>, dim3((pl.nb + 1023) / 1024, G), dim3(1024), 0, stream, ws.block_hist, pl.nb, ws.counts, sort_blocks, ws.heavy, ws.bucket_off, ws.sub_off,
-                       ws.totals, sub, heavy_min, MsmWorkspace::HEAVY_CAP, rs);
-  else
-    hipLaunchKernelGGL(k_scan<MSM_SUB>, dim3(1), dim3(1024), 0, stream, ws.counts, pl.nb, ws.bucket_off, ws.sub_off, ws.totals, sub, ws.heavy, heavy_min, MsmWorkspace::HEAVY_CAP);
-  VZ_EV(2);
-  if (lds_sort)
-    hipLaunchKernelGGL(k_scatter_lds<S>, dim3(sort_blocks, G), dim3(SORT_THREADS), pl.nb * 4, stream, d_scalars, n, scalars_mont, split_ones, sgn, pl.c, pl.K, bstride, pl.nb,
-                       pstride, ws.bucket_off, ws.block_hist, ws.sorted, rs);
-  else
-    hipLaunchKernelGGL(k_scatter<S>, dim3(gs), dim3(TB), 0, stream, d_scalars, n, scalars_mont, split_ones, sgn, pl.c, pl.K, bstride, pstride,
-                       ws.bucket_off, ws.cursor, ws.sorted);
-  VZ_EV(3);
-  uint32_t* partial = reinterpret_cast<uint32_t*>(ws.partial);
-  const unsigned ga = (unsigned)((max_subs + TB - 1) / TB);
-  // (accum_lds_kb, an experiment kept as an option: LDS the kernel never touches, so that only 160 / kb of its workgroups fit a CU whatever the number of
-  //  launches in flight and the critical chain's kernels — 180-230 registers a lane — always find room.  Measured zero-sum at two workgroups per CU and 2 %
-  //  worse at one, in the 20-row window, over 256 rows and on one chain: profiles/r05_segments_queues_sweep.txt)
-  const size_t accum_lds = (size_t)msm_tuning().accum_lds_kb * 1024;
-  if (accum_lds > 65536) { static const hipError_t once = hipFuncSetAttribute((const void*)k_accum<F>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); (void)once; }
-  hipLaunchKernelGGL(k_accum<F>, dim3(ga, G), dim3(TB), accum_lds, stream, d_bases, ws.sorted, ws.bucket_off, ws.sub_off, pl.nb,
-                     ws.totals, partial, sub, rs);
-  VZ_EV(4);
-  const unsigned per_wg = 256u >> lane_bits, nbn = (pl.nb + per_wg - 1) / per_wg;
-  hipLaunchKernelGGL(k_combine<F>, dim3(nbn + COMBINE_HEAVY_BLOCKS + COMBINE_SPLIT_BLOCKS, G), dim3(256), 0, stream, partial, ws.sub_off, pl.nb, nbn,
-                     (const uint32_t*)ws.heavy, MsmWorkspace::HEAVY_CAP, ws.heavy_scratch, lane_bits, heavy_min, ws.heavy_done, rs);
-  VZ_EV(5);      // (stage 2 of the very heavy buckets: the last of a bucket's workgroups, inside k_combine)
-  const unsigned T = pl.nbw < 256 ? pl.nbw : 256;
-  uint32_t* wsum = direct ? reinterpret_cast<uint32_t*>(pinned_dst) : reinterpret_cast<uint32_t*>(ws.window_sums);
-  const uint32_t vw = std::min<uint32_t>(pl.nbw, MSM_VWIN);      // shared bucket set: virtual windows of vw buckets
-  const int V = (int)(pl.nbw / vw);
-  const int kout = planes ? (int)Pl + 2 : tabled && !own ? 2 * V : pl.K;     // sums produced: planes + two plain halves; (R_v, S_v) per virtual window; or one per window
-  if (planes) {
-    hipLaunchKernelGGL(k_reduce_planes<F>, dim3((Pl + 2) * Gp), dim3(256), 0, stream, (const uint32_t*)partial, (const uint32_t*)ws.counts, (const uint32_t*)ws.sub_off, pl.nbw, Pl, Gp,
-                       pl.nbw / (512u * Gp), ws.plane_scratch, ws.totals + 3, wsum);
-  } else if (tabled && !own) {
-    hipLaunchKernelGGL(k_reduce<F>, dim3(V, G), dim3(vw < 256 ? vw : 256), 0, stream, (const uint32_t*)partial, (const uint32_t*)ws.counts, (const uint32_t*)ws.sub_off, vw, wsum, wsum + (size_t)XYZZ_WORDS * V, rs);
-  } else
-    hipLaunchKernelGGL(k_reduce<F>, dim3(pl.K, G), dim3(T), 0, stream, (const uint32_t*)partial, (const uint32_t*)ws.counts, (const uint32_t*)ws.sub_off, pl.nbw, wsum, (uint32_t*)nullptr, rs);
-  VZ_EV(6);
-#undef VZ_EV
-  if (split_ones && rg) {   // a group's unit sums -> each row's window_sums[K], and the caller's own, in two launches
-    OnesDesc ds[2 * MSM_ROWS_MAX];
-    for (uint32_t r = 0; r < G; r++) ds[r] = OnesDesc{d_scalars + 8 * r * rg->scalar_row_stride, d_bases, wsum + r * (rg->pinned_row_stride / 4) + (size_t)XYZZ_WORDS * kout, n};
-    for (uint32_t e = 0; e < rg->n_extra; e++) ds[G + e] = rg->extra[e];
-    VZ_HIP_CHECK(ones_launch_rows<C>(stream, ws, ds, G + rg->n_extra, scalars_mont));
-  } else if (split_ones) {   // sum of the bases with unit scalar -> window_sums[K]
-    uint32_t* lvl0 = reinterpret_cast<uint32_t*>(ws.ones_partial);
-    if (msm_tuning().ones_dense) hipLaunchKernelGGL((k_ones_dense<S, F>), dim3(ONES_THREADS / 256), dim3(256), 0, stream, d_scalars, d_bases, n, scalars_mont, lvl0);
-    else hipLaunchKernelGGL((k_ones_partial<S, F>), dim3(ONES_THREADS / 256), dim3(256), 0, stream, d_scalars, d_bases, n, scalars_mont, lvl0);
-    uint32_t* lvl1 = lvl0 + (size_t)XYZZ_WORDS * ONES_THREADS;
-    hipLaunchKernelGGL(k_tree256<F>, dim3(ONES_THREADS / 256), dim3(256), 0, stream, lvl0, ONES_THREADS, lvl1);
-    hipLaunchKernelGGL(k_tree256<F>, dim3(1), dim3(256), 0, stream, lvl1, ONES_THREADS / 256, wsum + (size_t)XYZZ_WORDS * kout);
-  }
-  VZ_HIP_CHECK(hipGetLastError());
-  if (!direct) VZ_HIP_CHECK(hipMemcpyAsync(pinned_dst, wsum, 4 * (size_t)XYZZ_WORDS * (kout + (split_ones ? 1 : 0)), hipMemcpyDeviceToHost, stream));
-  return hipSuccess;
 }
 
 template <class C>
@@ -1203,7 +1152,7 @@ hipError_t msm_launch_rows(hipStream_t stream, MsmWorkspace& ws, const uint32_t*
                            int scalars_mont, void* pinned_dst, size_t pinned_row_stride, MsmPlan* plan_out, int split_ones, const BaseTables* tb,
                            const OnesDesc* extra, uint32_t n_extra, uint32_t max_rows) {
   if (G > 1 && (scalar_row_stride < n || (pinned_row_stride & 15))) return hipErrorInvalidValue;
-  const MsmRowGroup rg{G, scalar_row_stride, pinned_row_stride, extra, n_extra, max_rows, nullptr};
+  const MsmRowGroup rg{G, scalar_row_stride, pinned_row_stride, extra, n_extra, max_rows};
   const hipError_t e = msm_launch_impl<C>(stream, ws, d_bases, d_scalars, n, scalars_mont, 0, pinned_dst, plan_out, nullptr, split_ones, tb, &rg);
   if (e != hipErrorNotSupported) return e;
   // a shape the grouped chain does not cover: row after row
@@ -1214,52 +1163,51 @@ hipError_t msm_launch_rows(hipStream_t stream, MsmWorkspace& ws, const uint32_t*
 }
 template <class C>
 size_t msm_rows_row_bytes(size_t n, int split_ones, const BaseTables* tb) {
-  size_t bytes = 0;
-  MsmWorkspace none; MsmPlan pl;
-  const MsmRowGroup rg{1, n, 0, nullptr, 0, 0, &bytes};
-  return msm_launch_impl<C>(nullptr, none, tb ? tb->d : nullptr, nullptr, n, 1, 0, nullptr, &pl, nullptr, split_ones, tb, &rg) == hipSuccess ? bytes : 0;
+  MsmShape sh;
+  MsmGroupDesc one_row; one_row.grouped = true;
+  if (msm_shape(sh, n, C::Scalar::Params::BITS, 0, split_ones, msm_table_desc(tb), one_row, msm_tuning(), msm_no_small()) != MSM_SHAPE_OK) return 0;
+  return MsmWorkspace::row_bytes(sh.plan.nb, sh.entries, sh.max_subs, (size_t)SORT_BLOCKS * sh.plan.nb);
 }
 
-// Host tail: Horner over the K window sums (converted to the standard form, whose host multiply is the fast 4x64 path)
-// and one inversion.  Result affine, standard Montgomery form.
+// One XYZZ point as the kernels store it (four coordinates of COORD_WORDS words, nine used) in the standard form, whose host multiply is the fast 4x64 path
 template <class C>
-Affine<typename C::Base> msm_finish(const MsmPlan& pl, const void* pinned) {
+static inline XYZZ<typename C::Base> host_point(const uint32_t* d) {
   typedef typename C::Coord F;
   typedef typename C::Base FS;
-  const uint32_t* hw = reinterpret_cast<const uint32_t*>(pinned);
-  auto host_point = [&](int w) {
-    XYZZ<FS> p; const uint32_t* d = hw + (size_t)XYZZ_WORDS * w;
-    FS* f[4] = {&p.X, &p.Y, &p.ZZ, &p.ZZZ};
-    for (int k = 0; k < 4; k++) { F t; for (int i = 0; i < 9; i++) t.v[i] = d[COORD_WORDS * k + i]; *f[k] = t.to_std(); }
-    return p;
-  };
+  XYZZ<FS> p; FS* f[4] = {&p.X, &p.Y, &p.ZZ, &p.ZZZ};
+  for (int k = 0; k < 4; k++) { F t; for (int i = 0; i < 9; i++) t.v[i] = d[COORD_WORDS * k + i]; *f[k] = t.to_std(); }
+  return p;
+}
+
+// Host tail: Horner over the window sums and one inversion.  Result affine, standard Montgomery form.  Which sums there are: msm_kout (msm_shape.hpp),
+// as the launcher wrote them; the unit sum, if any, is the one after them.
+template <class C>
+Affine<typename C::Base> msm_finish(const MsmPlan& pl, const void* pinned) {
+  typedef typename C::Base FS;
+  auto point = [&](int w) { return host_point<C>(reinterpret_cast<const uint32_t*>(pinned) + (size_t)XYZZ_WORDS * w); };
+  const int kout = msm_kout(pl);
   XYZZ<FS> acc = XYZZ<FS>::identity();
   if (pl.tabled == 4) {
     // bit planes of the shared bucket set (k_reduce_planes): Σ_p 2^p·S_p + plain low + plain high
-    int P = 0; while ((1u << P) < pl.nbw) P++;
-    for (int q = P - 1; q >= 0; q--) { acc = dbl(acc); add_full(acc, host_point(q)); }
-    add_full(acc, host_point(P)); add_full(acc, host_point(P + 1));
-    if (pl.split_ones) add_full(acc, host_point(P + 2));
-    return to_affine(acc);
-  }
-  if (pl.tabled == 1) {
+    const int P = (int)msm_plane_bits(pl);
+    for (int q = P - 1; q >= 0; q--) { acc = dbl(acc); add_full(acc, point(q)); }
+    add_full(acc, point(P)); add_full(acc, point(P + 1));
+  } else if (pl.tabled == 1) {
     // one bucket set shared by all windows, reduced as V virtual windows of MSM_VWIN buckets: bucket b = MSM_VWIN·v + idx weighs
     // (idx + 1) + MSM_VWIN·v, so the sum is  Σ_v R_v + MSM_VWIN·Σ_v v·S_v  with  Σ_v v·S_v = Σ_{s>=1} Σ_{v>=s} S_v
-    const uint32_t vw = pl.nbw < MSM_VWIN ? pl.nbw : MSM_VWIN;
-    const int V = (int)(pl.nbw / vw);
+    const uint32_t vw = msm_vwin(pl);
+    const int V = msm_vwindows(pl);
     XYZZ<FS> run = XYZZ<FS>::identity();
-    for (int v = V - 1; v >= 1; v--) { add_full(run, host_point(V + v)); add_full(acc, run); }
+    for (int v = V - 1; v >= 1; v--) { add_full(run, point(V + v)); add_full(acc, run); }
     for (uint32_t k = 1; k < vw; k <<= 1) acc = dbl(acc);
-    for (int v = 0; v < V; v++) add_full(acc, host_point(v));
-    if (pl.split_ones) add_full(acc, host_point(2 * V));
-    return to_affine(acc);
+    for (int v = 0; v < V; v++) add_full(acc, point(v));
+  } else {      // K sums; tabled == 2, 3: of one bucket set each, already weighted
+    for (int w = kout - 1; w >= 0; w--) {
+      if (!pl.tabled) for (int k = 0; k < pl.c; k++) acc = dbl(acc);
+      add_full(acc, point(w));
+    }
   }
-  const int kout = pl.K;      // tabled == 2, 3: K sums of one bucket set each, already weighted
-  for (int w = kout - 1; w >= 0; w--) {
-    if (!pl.tabled) for (int k = 0; k < pl.c; k++) acc = dbl(acc);
-    add_full(acc, host_point(w));
-  }
-  if (pl.split_ones) add_full(acc, host_point(kout));
+  if (pl.split_ones) add_full(acc, point(kout));
   return to_affine(acc);
 }
 
@@ -1297,12 +1245,7 @@ hipError_t ones_launch_rows(hipStream_t stream, MsmWorkspace& ws, const OnesDesc
 }
 template <class C>
 XYZZ<typename C::Base> ones_finish(const void* pinned) {
-  typedef typename C::Coord F;
-  typedef typename C::Base FS;
-  const uint32_t* d = reinterpret_cast<const uint32_t*>(pinned);
-  XYZZ<FS> p; FS* f[4] = {&p.X, &p.Y, &p.ZZ, &p.ZZZ};
-  for (int k = 0; k < 4; k++) { F t; for (int i = 0; i < 9; i++) t.v[i] = d[COORD_WORDS * k + i]; *f[k] = t.to_std(); }
-  return p;
+  return host_point<C>(reinterpret_cast<const uint32_t*>(pinned));
 }
 
 template <class C>
