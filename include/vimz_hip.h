@@ -523,8 +523,9 @@ int vimz_decider_info(const vimz_decider* d, uint64_t info[8]);
  * gamma, delta (G2: x.c0, x.c1, y.c0, y.c1), the number of IC points, the IC points, KZG G_1 (G1), G_2, VK (G2); returns the byte size (copies
  * when cap suffices) */
 int64_t vimz_decider_vk(const vimz_decider* d, void* buf, size_t cap);
-/* The key pair at rest (bytes; layout: vimz_amd/csrc/groth16.hip): a set-up made once per circuit, or keys made elsewhere — a ceremony's, converted to this
- * layout: the library then never sees a trapdoor.  _save returns the byte size (copies when cap suffices); _load checks sizes, the public-parameter hash and the
+/* The key pair at rest (bytes; layout: vimz_amd/csrc/groth16.hip): a set-up made once per circuit, or a key made elsewhere in this layout (the library then never
+ * sees its trapdoor).  Nothing in the library makes such a key yet: no ceremony has one for THIS circuit, and deriving it from a ceremony's powers of tau is
+ * DESIGN.md §8 item 5.  _save returns the byte size (copies when cap suffices); _load checks sizes, the public-parameter hash and the
  * verifying part's points, and takes the queries as they are (a loaded key is trusted like any common reference string). */
 int64_t vimz_decider_key_save(vimz_decider* d, void* buf, size_t cap);
 int vimz_decider_key_load(vimz_cf* prover, const void* buf, size_t len, vimz_decider** out);

@@ -62,6 +62,52 @@ def read_wtns(data):
     return prime, np.frombuffer(sec[2], dtype=np.uint64).reshape(n, 4).copy()
 
 
+BN254_Q = 21888242871839275222246405745257275088696311157297823662689037894645226208583
+_PTAU_SECTIONS = ((2, "tau_g1", 64), (3, "tau_g2", 128), (4, "alpha_g1", 64), (5, "beta_g1", 64), (6, "beta_g2", 128))      # section, name, bytes per point
+
+
+def read_ptau(data):
+    """A powers-of-tau file (snarkjs's `.ptau` container, magic "ptau") -> dict(power, ceremony_power, tau_g1, tau_g2, alpha_g1, beta_g1, beta_g2): read-only
+    uint64 views of `data` (no copy), one row per point, 4 words per coordinate, in the file's own (Montgomery) form.  Sections: 1 = n8, the prime, the power,
+    the ceremony's power; 2 tau_g1 (2^(power+1) − 1 points), 3 tau_g2, 4 alpha_g1, 5 beta_g1 (2^power each), 6 beta_g2 (one).  Points are affine and
+    uncompressed, every coordinate 32 bytes little-endian in Montgomery form, G2 as x.c0, x.c1, y.c0, y.c1.  UNPINNED: the layout is restated from snarkjs's
+    published format and this reader has not yet read a real ceremony file.  ValueError for a truncated container, a missing section, a prime other than BN254's
+    q and section lengths that do not match the power; the points themselves are not judged here."""
+    data = bytes(data)
+    try:
+        sec = _sections(data, b"ptau")
+    except struct.error:
+        raise ValueError("ptau: the file ends inside its section table") from None
+    pos = 12
+    for _ in range(struct.unpack_from("<I", data, 8)[0]):      # (slices past the end come back short without a complaint)
+        pos += 12 + struct.unpack_from("<Q", data, pos + 4)[0]
+        if pos > len(data):
+            raise ValueError("ptau: the file ends inside a section")
+    hdr = sec.get(1)
+    if hdr is None:
+        raise ValueError("ptau: no header section")
+    if len(hdr) < 4 or struct.unpack_from("<I", hdr, 0)[0] != 32:
+        raise ValueError("ptau header: only 32-byte field elements are supported")
+    if len(hdr) != 4 + 32 + 8:
+        raise ValueError(f"ptau header: {len(hdr)} bytes, expected 44 (n8, the prime, the power, the ceremony's power)")
+    if int.from_bytes(hdr[4:36], "little") != BN254_Q:
+        raise ValueError("ptau header: the prime is not BN254's base field modulus")
+    power, ceremony_power = struct.unpack_from("<II", hdr, 36)
+    if not 1 <= power <= 26:
+        raise ValueError("ptau header: power outside 1..26")
+    n2 = 1 << power
+    out = {"power": power, "ceremony_power": ceremony_power}
+    for t, name, size in _PTAU_SECTIONS:
+        points = {"tau_g1": 2 * n2 - 1, "beta_g2": 1}.get(name, n2)
+        body = sec.get(t)
+        if body is None:
+            raise ValueError(f"ptau section {t} ({name}) is missing")
+        if len(body) != points * size:
+            raise ValueError(f"ptau section {t} ({name}): {len(body)} bytes, the power asks for {points * size}")
+        out[name] = np.frombuffer(body, dtype="<u8").reshape(points, size // 8)
+    return out
+
+
 def to_nova_columns(r1cs):
     """The matrices with circom wire j moved to nova-snark's column: j = 0 -> the u slot, 1 <= j <= n_pub -> X, the rest -> W.
     -> (n_witness, n_public, A, B, C)."""
