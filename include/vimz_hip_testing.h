@@ -81,6 +81,10 @@ int vimz_test_g16_fixed_mul(vimz_ctx* ctx, int group, const uint64_t* scalars, s
 /* the proof's G2 multi-scalar multiplication on a caller's query: sum of wires[idx[i]]·P_i over n >= 1 points of G2 (canonical, 16 words each, the identity as
  * zeros), m >= n wire values of 4 words (form = VIMZ_FORM_*) and n wire numbers below m.  out_xy: the affine sum, canonical, the identity as zeros. */
 int vimz_test_g16_g2_msm(vimz_ctx* ctx, const uint64_t* bases_xy, size_t n, const uint64_t* wires, size_t m, int form, const uint32_t* idx, uint64_t out_xy[16]);
+/* The same-scalar multiplication of a set-up from a powers-of-tau string (vimz_amd/csrc/g16_powers.hip: g16_scale_points, k_scale_points), in place as the
+ * set-up uses it: out_i = scalar · P_i for n >= 1 points of G1 (canonical, 8 words each, the identity as zeros; each on the curve) and one canonical scalar
+ * below r.  out_xy: n affine points, canonical, the identity as zeros. */
+int vimz_test_g16_scale_points(vimz_ctx* ctx, const uint64_t* points_xy, size_t n, const uint64_t scalar[4], uint64_t* out_xy);
 /* The chains of the full decider's check 5 (vimz_amd/csrc/aug/decider_cf.hpp: every scalar walks the 127 two-bit windows of its generator's table by affine
  * additions from the derived generator H) over a caller's generators and scalars, through the functions the prover calls: where = 0 the host's
  * (cf_open_chains_host; ctx may be NULL), where = 1 the device's (k_cf_open_chains, the scalars uploaded in Montgomery form as the prover holds them, both

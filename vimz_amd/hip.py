@@ -868,6 +868,32 @@ def kzg_setup(ctx, n, seed=None):
     return Bases(ctx, h, L.CURVE_BN254_G1, n), vk
 
 
+_BN254_Q = 21888242871839275222246405745257275088696311157297823662689037894645226208583
+
+
+def kzg_from_powers(ctx, powers, n):
+    """KZG's keys from a powers-of-tau string (iden3.read_ptau's dictionary: rows of uint64 words in the file's Montgomery form) instead of kzg_setup: the srs is
+    the string's first n points [tau^k]G1 as Bases, vk_g2 = [tau]G2 = tau_g2[1] as the canonical (4, 4) array Decider takes — no tau is drawn in this process, and
+    a decider key derived from the same string shares its tau (as snarkjs's set-ups over one `.ptau` do).  VimzError(ERR_INVALID): n below 2 (the decider checks
+    e(srs[1], G2) = e(G1, vk)), a string shorter than n, a first power that is not the generator, a coordinate of tau_g2[1] not below q.  The points are not
+    judged otherwise: that pairing check is the decider's, the same-ratio check of every power is nobody's yet."""
+    g1 = np.ascontiguousarray(powers["tau_g1"], dtype=np.uint64).reshape(-1, 8)
+    g2 = np.ascontiguousarray(powers["tau_g2"], dtype=np.uint64).reshape(-1, 16)
+    n = int(n)
+    if n < 2 or n > g1.shape[0] or g2.shape[0] < 2:
+        raise L.VimzError(L.ERR_INVALID, f"kzg_from_powers: n = {n} with {g1.shape[0]} powers in G1 and {g2.shape[0]} in G2 (needs 2 <= n <= the string's length)")
+    ints = lambda row: [int.from_bytes(row[4 * i:4 * i + 4].tobytes(), "little") for i in range(row.size // 4)]      # noqa: E731
+    mont = 1 << 256
+    if ints(g1[0]) != [mont % _BN254_Q, 2 * mont % _BN254_Q]:
+        raise L.VimzError(L.ERR_INVALID, "kzg_from_powers: tau_g1[0] is not the generator of G1")
+    vk = ints(g2[1])
+    if max(vk) >= _BN254_Q:
+        raise L.VimzError(L.ERR_INVALID, "kzg_from_powers: a coordinate of tau_g2[1] is not below the modulus")
+    minv = pow(mont, -1, _BN254_Q)
+    vk_words = np.frombuffer(b"".join((c * minv % _BN254_Q).to_bytes(32, "little") for c in vk), dtype="<u8").reshape(4, 4).astype(np.uint64)
+    return ctx.bases_upload(L.CURVE_BN254_G1, g1[:n], form=L.FORM_MONTGOMERY), vk_words
+
+
 def _seeded(ctx, name):
     if not hasattr(ctx.lib, name):
         raise RuntimeError(f"{name} exists only in libvimz_hip_testing.so (start the process with VIMZ_HIP_LIBRARY=testing): seeded setups are test hooks")
