@@ -509,6 +509,17 @@ typedef struct vimz_decider vimz_decider;
 /* KZG::setup (inside `prepare_folding`, vimz/src/sonobe_backend/folding.rs:36-48): srs = [tau^i]G1 for i < n as a commitment key (use it as
  * ck_main of vimz_cf_create), vk_g2_out = [tau]G2 (x.c0, x.c1, y.c0, y.c1 canonical).  tau comes from the OS's randomness and is forgotten. */
 int vimz_kzg_setup(vimz_ctx* ctx, size_t n, vimz_bases** srs_out, uint64_t vk_g2_out[16]);
+/* The Lagrange basis of a powers-of-tau string's points (what snarkjs's `powersoftau prepare phase2` computes; the first step of a Groth16 set-up that draws no
+ * trapdoor): out[j] = L_j = 1/n · sum_k w^(−jk)·points[k] over the first n = 2^logn points, w the primitive n-th root of unity
+ * 5^((r−1)/n) of Fr — [L_j(tau)]G when points[k] = [tau^k]G, so that sum_j e_j·out[j] commits to the polynomial with the evaluations e_j.  group = 1: points of
+ * BN254 G1, 8 words each (x, y); group = 2: of G2, 16 words (x.c0, x.c1, y.c0, y.c1).  form = VIMZ_FORM_* of the coordinates, `out` in the same form; the identity
+ * is zeros on both sides.  The inverse transform over points runs on the GPU (radix 2, one launch per stage, logn·n/2 scalar multiplications), on the
+ * context's stream and under the context's lock like every call on a context: it does not overlap a fold on the same context (a set-up that must run under a
+ * fold needs a stream of its own).  VIMZ_ERR_INVALID: a NULL pointer, a group other than 1 or 2, logn outside 1..26, n_points < 2^logn, a coordinate not below
+ * q, a point not on its curve.  NOT judged: membership of the order-r subgroup of G2, and that the points are the powers of one tau (the same-ratio check of
+ * the string) — the caller vouches for the string.  seconds (optional) = {host conversion and checks, device (upload, transform, download)}. */
+int vimz_powers_lagrange(vimz_ctx* ctx, int group /* 1: G1, 8 words a point; 2: G2, 16 words: x.c0 x.c1 y.c0 y.c1 */, const uint64_t* points, size_t n_points,
+                         int form, int logn, uint64_t* out, double seconds[2]);
 /* Decider::preprocess.  prover: supplies shapes, keys and context (must outlive the object).  kzg_vk_g2 (optional): [tau]G2 of the SRS the prover's
  * ck_main is made of (needed by vimz_decider_verify; part of vimz_decider_vk; checked against that SRS: e(srs[1], G2) = e(G1, [tau]G2)).
  * light: 0 = the full decider (the reference's default), non-zero = the `light-test` variant.  The full decider bakes the first generators of the

@@ -85,6 +85,11 @@ int vimz_test_g16_g2_msm(vimz_ctx* ctx, const uint64_t* bases_xy, size_t n, cons
  * set-up uses it: out_i = scalar · P_i for n >= 1 points of G1 (canonical, 8 words each, the identity as zeros; each on the curve) and one canonical scalar
  * below r.  out_xy: n affine points, canonical, the identity as zeros. */
 int vimz_test_g16_scale_points(vimz_ctx* ctx, const uint64_t* points_xy, size_t n, const uint64_t scalar[4], uint64_t* out_xy);
+/* The transform over points of the same set-up (g16_point_transform: k_pt_twiddles, k_pt_bitrev, one k_pt_stage per stage, k_scale_points), in place on the
+ * device as vimz_powers_lagrange runs it, in every direction: out_j = sum_k w^(jk)·P_k over the 2^logn points, logn in 1..26, w the domain's root of unity
+ * (tests/_g16_ref.omega) or, with inverse != 0, its inverse; with scaled != 0 times 1/n.  group = 1: points of G1, 8 words each; 2: of G2, 16 words (x.c0, x.c1,
+ * y.c0, y.c1).  Canonical on both sides, the identity as zeros; every input below q and on its curve. */
+int vimz_test_g16_point_transform(vimz_ctx* ctx, int group, int logn, int inverse, int scaled, const uint64_t* points, uint64_t* out);
 /* The chains of the full decider's check 5 (vimz_amd/csrc/aug/decider_cf.hpp: every scalar walks the 127 two-bit windows of its generator's table by affine
  * additions from the derived generator H) over a caller's generators and scalars, through the functions the prover calls: where = 0 the host's
  * (cf_open_chains_host; ctx may be NULL), where = 1 the device's (k_cf_open_chains, the scalars uploaded in Montgomery form as the prover holds them, both

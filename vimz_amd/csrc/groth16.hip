@@ -65,13 +65,15 @@ Fe fr_from_hash(const void* seed, size_t n, const char* tag) {      // an elemen
   Fe c; memcpy(c.v, d, 32);
   return Fe::to_mont(c);
 }
-// a primitive 2^k-th root of unity of Fr: 5 generates the multiplicative group, r - 1 = 2^28 · odd
+}  // namespace
+// a primitive 2^k-th root of unity of Fr: 5 generates the multiplicative group, r - 1 = 2^28 · odd  (g16_powers.hpp: the transform over points uses it too)
 Fe fr_root_of_unity(int k) {
   uint32_t e[8]; uint64_t br = 1;
   for (int i = 0; i < 8; i++) { const uint64_t d = (uint64_t)BnFr::MOD.w[i] - br; e[i] = (uint32_t)d; br = (d >> 32) & 1; }      // r - 1
   for (int s = 0; s < k; s++) { for (int i = 0; i < 8; i++) e[i] = (e[i] >> 1) | (i < 7 ? e[i + 1] << 31 : 0u); }                 // >> k (exact: k <= 28)
   return fr_pow(cb::f_from_u64<Fe>(5), e);
 }
+namespace {
 
 // ---- kernels --------------------------------------------------------------------------------------------------------------------------------
 // out[i] = s_i · G for a fixed base G: T[w][d] = d · 2^(4w) · G (64 windows of 16 multiples) turns a multiplication into at most 64 mixed additions

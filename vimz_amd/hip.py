@@ -894,6 +894,42 @@ def kzg_from_powers(ctx, powers, n):
     return ctx.bases_upload(L.CURVE_BN254_G1, g1[:n], form=L.FORM_MONTGOMERY), vk_words
 
 
+_LAGRANGE_ARRAYS = (("tau_g1", 1), ("alpha_g1", 1), ("beta_g1", 1), ("tau_g2", 2))      # name, group
+
+
+def powers_lagrange(ctx, group, points, logn, form=L.FORM_CANONICAL, seconds=None):
+    """vimz_powers_lagrange: the first 2^logn of `points` (rows of 8 words for group 1 = G1, of 16 for group 2 = G2) -> the points [L_j] in the same form, the
+    inverse transform over points on the GPU.  seconds: a list that receives [host conversion and checks, device]."""
+    pts = _u64(points).reshape(-1, 8 * group)
+    out = np.zeros((1 << logn, 8 * group), dtype=np.uint64)
+    sec = (C.c_double * 2)()
+    ctx.lib.vimz_powers_lagrange.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
+    ctx._chk(ctx.lib.vimz_powers_lagrange(ctx.h, group, _ptr(pts), pts.shape[0], form, logn, _ptr(out), sec))
+    if seconds is not None:
+        seconds[:] = list(sec)
+    return out
+
+
+def lagrange_from_powers(ctx, powers, logn):
+    """The Lagrange bases of a powers-of-tau string (iden3.read_ptau's dictionary: rows of uint64 words in the file's Montgomery form) over the domain of
+    n = 2^logn points: {"tau_g1", "alpha_g1", "beta_g1": (n, 8), "tau_g2": (n, 16)} in the same form, row j = [L_j(tau)]G1, [alpha·L_j(tau)]G1, [beta·L_j(tau)]G1,
+    [L_j(tau)]G2 — what snarkjs's `powersoftau prepare phase2` derives, by four calls of vimz_powers_lagrange (the inverse transform over points, on the GPU).
+    With them a commitment to a polynomial given by its evaluations e is ctx.msm over the tau_g1 rows and e.  VimzError(ERR_INVALID), before any GPU work: logn
+    below 1 or above the string's power, an array shorter than n; from the library: a coordinate not below q, a point not on its curve.  Subgroup membership
+    in G2 and the same-ratio property of the string are not judged."""
+    logn = int(logn)
+    if logn < 1 or logn > int(powers["power"]):
+        raise L.VimzError(L.ERR_INVALID, f"lagrange_from_powers: logn = {logn} with a string of power {int(powers['power'])} (needs 1 <= logn <= the power)")
+    n = 1 << logn
+    arrays = {}
+    for name, group in _LAGRANGE_ARRAYS:
+        a = np.ascontiguousarray(powers[name], dtype=np.uint64).reshape(-1, 8 * group)
+        if a.shape[0] < n:
+            raise L.VimzError(L.ERR_INVALID, f"lagrange_from_powers: {name} holds {a.shape[0]} points, the domain has {n}")
+        arrays[name] = a[:n]
+    return {name: powers_lagrange(ctx, group, arrays[name], logn, form=L.FORM_MONTGOMERY) for name, group in _LAGRANGE_ARRAYS}
+
+
 def _seeded(ctx, name):
     if not hasattr(ctx.lib, name):
         raise RuntimeError(f"{name} exists only in libvimz_hip_testing.so (start the process with VIMZ_HIP_LIBRARY=testing): seeded setups are test hooks")

@@ -5,6 +5,7 @@ seam-based accumulator (`vimz_amd.nifs`).  (The native reader `vimz_circuit_load
 Column order: circom numbers the wires [1 | public outputs | public inputs | private]; nova-snark's R1CSShape orders an assignment
 z = [W (private wires) | u | X (public wires)] — `to_nova_columns` maps one onto the other the way nova-scotia's CircomCircuit does."""
 import struct
+import sys
 
 import numpy as np
 
@@ -128,3 +129,28 @@ def split_witness(r1cs, wtns_values):
         raise ValueError("witness does not fit the circuit (length, or wire 0 is not 1)")
     X = [sum(int(l) << (64 * i) for i, l in enumerate(row)) for row in v[1:1 + n_pub]]
     return v[1 + n_pub:], X
+
+
+def _main(argv):
+    """python -m vimz_amd.iden3 lagrange FILE.ptau LOGN OUT.npz: the string's Lagrange bases over the domain of 2^LOGN points (hip.lagrange_from_powers, on GPU 0)
+    as an .npz of tau_g1, alpha_g1, beta_g1 (n, 8) and tau_g2 (n, 16) in the file's Montgomery form, with logn."""
+    if len(argv) != 4 or argv[0] != "lagrange":
+        print("usage: python -m vimz_amd.iden3 lagrange FILE.ptau LOGN OUT.npz", file=sys.stderr)
+        return 2
+    from . import hip
+    with open(argv[1], "rb") as fp:
+        powers = read_ptau(fp.read())
+    logn = int(argv[2])
+    ctx = hip.Context(0)
+    try:
+        bases = hip.lagrange_from_powers(ctx, powers, logn)
+    finally:
+        ctx.close()
+    with open(argv[3], "wb") as fp:          # (a file object: savez leaves its name alone)
+        np.savez(fp, logn=np.int64(logn), **bases)
+    print(f"lagrange: {1 << logn} points each of tau_g1, alpha_g1, beta_g1, tau_g2 -> {argv[3]}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(_main(sys.argv[1:]))
