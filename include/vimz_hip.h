@@ -527,6 +527,19 @@ int vimz_powers_lagrange(vimz_ctx* ctx, int group /* 1: G1, 8 words a point; 2: 
  * setup; seeded test setups exist only in libvimz_hip_testing.so).  seconds (optional) = {circuit synthesis, QAP evaluation at the trapdoor, key
  * points on the GPU, total} */
 int vimz_decider_setup(vimz_cf* prover, const uint64_t kzg_vk_g2[16], int light, vimz_decider** out, double seconds[4]);
+/* Decider::preprocess from a powers-of-tau string (iden3.read_ptau's arrays: tau_g1 2n − 1 or more points [tau^k]G1, tau_g2, alpha_g1, beta_g1 n or more points
+ * each — n_pow of them —, beta_g2 one point; G1 points 8 words, G2 points 16 (x.c0, x.c1, y.c0, y.c1); form = VIMZ_FORM_* of the coordinates), n the circuit's domain
+ * (vimz_decider_info).  The Groth16 key is derived by group operations on the GPU — the four Lagrange bases by the inverse transform over points, the a, b and K
+ * queries as column sums of the matrices over them, l and h scaled by 1/delta — so tau, alpha and beta are the string's and never in this process; gamma = 1;
+ * delta comes from the OS's randomness and is wiped after use: the key's trust rests on the string plus this one local delta.  The KZG verifying key is the
+ * string's tau_g2[1], so the prover's ck_main must be the SRS of the same string (hip.kzg_from_powers).  VIMZ_ERR_INVALID with a message: a NULL pointer,
+ * n_pow < n or n_tau_g1 < 2n − 1, a coordinate not below q, a point not on its curve, tau_g1[0] or tau_g2[0] not the generator, beta_g2 or tau_g2[1] outside
+ * the subgroup, e(tau_g1[1], G2) != e(G1, tau_g2[1]), e(beta_g1[0], G2) != e(G1, beta_g2), tau_g2[1] not matching the prover's SRS.  NOT judged: the
+ * same-ratio property of the whole string (that every point is the next power of ONE tau, alpha·, beta· included) and subgroup membership of the other points of
+ * tau_g2 — the caller vouches for the string, as for vimz_powers_lagrange.  The resulting object is an ordinary decider (prove, verify, vk, key_save).
+ * seconds (optional) = {circuit synthesis, checks + upload, transforms, column sums, l/h scaling + key tables, total}. */
+int vimz_decider_setup_from_powers(vimz_cf* prover, int light, const uint64_t* tau_g1, size_t n_tau_g1, const uint64_t* tau_g2, const uint64_t* alpha_g1,
+                                   const uint64_t* beta_g1, size_t n_pow, const uint64_t beta_g2[16], int form, vimz_decider** out, double seconds[6]);
 void vimz_decider_free(vimz_decider* d);
 /* info = {constraints, wires, public inputs (36 + 2 len_z), domain size, non-zeros of A, B, C, rows of the CycleFold checks (0: light decider)} */
 int vimz_decider_info(const vimz_decider* d, uint64_t info[8]);
@@ -535,8 +548,8 @@ int vimz_decider_info(const vimz_decider* d, uint64_t info[8]);
  * when cap suffices) */
 int64_t vimz_decider_vk(const vimz_decider* d, void* buf, size_t cap);
 /* The key pair at rest (bytes; layout: vimz_amd/csrc/groth16.hip): a set-up made once per circuit, or a key made elsewhere in this layout (the library then never
- * sees its trapdoor).  Nothing in the library makes such a key yet: no ceremony has one for THIS circuit, and deriving it from a ceremony's powers of tau is
- * DESIGN.md §8 item 5.  _save returns the byte size (copies when cap suffices); _load checks sizes, the public-parameter hash and the
+ * sees its trapdoor).  vimz_decider_setup_from_powers makes such a key from a ceremony's powers of tau with one local delta; further
+ * delta contributions to a saved key are a follow-up.  _save returns the byte size (copies when cap suffices); _load checks sizes, the public-parameter hash and the
  * verifying part's points, and takes the queries as they are (a loaded key is trusted like any common reference string). */
 int64_t vimz_decider_key_save(vimz_decider* d, void* buf, size_t cap);
 int vimz_decider_key_load(vimz_cf* prover, const void* buf, size_t len, vimz_decider** out);

@@ -90,6 +90,22 @@ int vimz_test_g16_scale_points(vimz_ctx* ctx, const uint64_t* points_xy, size_t 
  * (tests/_g16_ref.omega) or, with inverse != 0, its inverse; with scaled != 0 times 1/n.  group = 1: points of G1, 8 words each; 2: of G2, 16 words (x.c0, x.c1,
  * y.c0, y.c1).  Canonical on both sides, the identity as zeros; every input below q and on its curve. */
 int vimz_test_g16_point_transform(vimz_ctx* ctx, int group, int logn, int inverse, int scaled, const uint64_t* points, uint64_t* out);
+/* The column sums of the same set-up (g16_colsum_plan.hpp: colsum_plan, then g16_column_sums: one k_col_runs launch per level of the plan — the very two calls
+ * vimz_decider_setup_from_powers makes): out_j = sum over the entries (r, k) with col[k] = j of dict[coef[k]]·P_r for a CSR matrix of n_rows rows (row_ptr: n_rows
+ * + 1 offsets) and n_cols >= 1 columns, n_dict >= 1 canonical coefficients below r of 4 words, and n_rows points.  group = 1: points of G1, 8 words each; 2: of
+ * G2, 16 words.  form = VIMZ_FORM_* of the points' coordinates, out (n_cols points) in the same form; the identity as zeros; every input below q and on its curve. */
+int vimz_test_g16_column_sums(vimz_ctx* ctx, int group, const uint32_t* row_ptr, const uint32_t* col, const uint32_t* coef, size_t n_rows, size_t n_cols,
+                              const uint64_t* dict, size_t n_dict, const uint64_t* points, int form, uint64_t* out);
+/* The h query of the same set-up (g16_h_query: k_point_diff, then k_scale_points in place): out_j = delta_inv·(P_(j+n) − P_j) for j < n − 1 over 2n − 1 points of
+ * G1, n >= 2, and one canonical scalar below r.  Canonical on both sides, 8 words a point, the identity as zeros. */
+int vimz_test_g16_h_query(vimz_ctx* ctx, const uint64_t* tau_g1_xy, size_t n, const uint64_t delta_inv[4], uint64_t* out_xy);
+/* The two set-ups a test compares byte for byte (vimz_decider_key_save): the trapdoor set-up (decider_setup_impl) with a GIVEN trapdoor — tau, alpha, beta, gamma,
+ * delta: 4 canonical words each, non-zero, below r — and vimz_decider_setup_from_powers with a given delta.  Whoever knows these scalars can forge. */
+int vimz_testing_decider_setup_trapdoor(vimz_cf* prover, const uint64_t kzg_vk_g2[16], int light, const uint64_t td[20] /* tau, alpha, beta, gamma, delta */,
+                                        vimz_decider** out, double seconds[4]);
+int vimz_testing_decider_setup_from_powers_delta(vimz_cf* prover, int light, const uint64_t* tau_g1, size_t n_tau_g1, const uint64_t* tau_g2, const uint64_t* alpha_g1,
+                                                 const uint64_t* beta_g1, size_t n_pow, const uint64_t beta_g2[16], int form, const uint64_t delta[4], vimz_decider** out,
+                                                 double seconds[6]);
 /* The chains of the full decider's check 5 (vimz_amd/csrc/aug/decider_cf.hpp: every scalar walks the 127 two-bit windows of its generator's table by affine
  * additions from the derived generator H) over a caller's generators and scalars, through the functions the prover calls: where = 0 the host's
  * (cf_open_chains_host; ctx may be NULL), where = 1 the device's (k_cf_open_chains, the scalars uploaded in Montgomery form as the prover holds them, both

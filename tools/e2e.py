@@ -2,12 +2,14 @@
 """End-to-end run of one transformation on the GPU, the way `vimz -b nova-snark -f <t>` sequences it
 (vimz/src/nova_snark_backend/mod.rs:22-80): prepare input -> prepare folding (circuit + key) -> fold every row -> verify.
 Prints the span times the reference logs ("Prepare input", "Prepare folding", "Fold input", "Verify folded proof").
-usage: e2e.py <transformation> <resolution> [segments] [ivc|accumulator|cyclefold] [proof file prefix or -] [witness batch]
+usage: e2e.py <transformation> <resolution> [segments] [ivc|accumulator|cyclefold] [proof file prefix or -] [witness batch] [--ptau FILE]
 ivc (default): ONE proof object — the rows are proven as `segments` Nova IVCs of contiguous row segments folded concurrently and
 merged (vimz_ivc_merge), then compressed;
 accumulator: NIFS accumulators of the segments merged by a final fold;
 cyclefold: the Sonobe backend's sequence (vimz/src/sonobe_backend/mod.rs:52-95: prepare folding, fold input, verify folded proof) with Nova +
-CycleFold; with one segment also the decider (Prepare decider, Generate decider proof: vimz_decider_*; the full one, or VIMZ_E2E_DECIDER=light) and the calldata bytes."""
+CycleFold; with one segment also the decider (Prepare decider, Generate decider proof: vimz_decider_*; the full one, or VIMZ_E2E_DECIDER=light) and the calldata bytes.
+--ptau FILE (cyclefold only): the KZG SRS and the decider's key come from that powers-of-tau string (iden3.read_ptau, hip.kzg_from_powers, hip.Decider(powers=))
+instead of a tau and a trapdoor drawn in this process."""
 import json
 import sys
 import time
@@ -21,6 +23,13 @@ from vimz_amd.distributed import fold_local_segments, fold_segments_merged  # no
 
 
 def main():
+    powers = None
+    if "--ptau" in sys.argv:
+        k = sys.argv.index("--ptau")
+        from vimz_amd import iden3
+        with open(sys.argv[k + 1], "rb") as fp:
+            powers = iden3.read_ptau(fp.read())
+        del sys.argv[k:k + 2]
     t, res = sys.argv[1], sys.argv[2]
     S = int(sys.argv[3]) if len(sys.argv) > 3 else 3      # (a lone, cold image: three segments — a fourth pays for itself only over repeated proofs, profiles/r06_segments_sweep.txt)
     mode = sys.argv[4] if len(sys.argv) > 4 else "ivc"
@@ -42,7 +51,9 @@ def main():
     t0 = time.time()
     # (contexts, step circuit, keys and the segments' provers side by side: folding.prepare_folding_overlapped)
     pmode = mode if mode in ("ivc", "cyclefold") else "accumulator"
-    ctxs, circuit, params, made, setup_split = folding.prepare_folding_overlapped(0, S, t, res, mode=pmode, batch=batch)
+    if powers is not None and mode != "cyclefold":
+        sys.exit("e2e.py: --ptau goes with the cyclefold mode")
+    ctxs, circuit, params, made, setup_split = folding.prepare_folding_overlapped(0, S, t, res, mode=pmode, batch=batch, powers=powers)
     batch = batch or folding.default_batch(circuit)
     th_in.join()
     rows, z0 = inp["rows"], inp["z0"]
@@ -91,7 +102,7 @@ def main():
             def _prep_decider():
                 t_d = time.time()
                 try:
-                    dec_box["dec"] = hip.Decider(cfs[0], kzg_vk=params.kzg_vk, light=light_decider)
+                    dec_box["dec"] = params.decider(cfs[0], light=light_decider)
                 except BaseException as e:      # noqa: BLE001
                     dec_box["err"] = e
                 dec_box["seconds"] = time.time() - t_d

@@ -6,6 +6,7 @@
 // butterflies (half = 1, 2, .., n/2).  Butterfly `index` of a stage works on the slots lo = 2·half·(index / half) + index % half and lo + half alone, so a stage
 // in place is race-free with one thread per butterfly, and the stages are sequenced by whoever launches them.
 #pragma once
+#include "g16_colsum_plan.hpp"
 #include "pairing.hpp"
 
 namespace vz {
@@ -62,6 +63,52 @@ VZ_HD void pt_butterfly(size_t index, size_t half, size_t n_half, Affine<F>* poi
   add_mixed(dif, u);
   points[lo] = to_affine(sum);
   points[hi] = to_affine(dif);
+}
+
+// ---- the column sums and the h query of the set-up (k_col_runs, k_point_diff): what ONE thread does, looped on the CPU by tests/native/colsum_plan_check.cpp ----
+
+// k·p over exactly `bits` bits of k (the host's plan knows bitlen(k)): the top bit's doubling of the identity is a compare and a branch
+template <class F>
+VZ_HD XYZZ<F> pt_scalar_mul_bits(const Affine<F>& p, const uint32_t* k, int bits) {
+  XYZZ<F> acc = XYZZ<F>::identity();
+#pragma unroll 1
+  for (int b = bits - 1; b >= 0; b--) {
+    acc = dbl(acc);
+    if ((k[b >> 5] >> (b & 31)) & 1u) add_mixed(acc, p);
+  }
+  return acc;
+}
+
+// run `index` of a level of g16_colsum_plan.hpp's plan: S = Σ ±src[..] over the run's entries (level 0: `entries` names point and sign; above: entries is NULL and
+// src the previous level's partials), then |c|·S when |c| is not one, written as a canonical affine point to the run's own slot — of `partials`, or of `out`.
+// add_mixed skips an identity, doubles equal points and restarts after opposite ones.  Every bound (len, bits) is the plan's; nothing another thread writes is read.
+template <class F>
+VZ_HD void colsum_run(size_t index, const ColsumRun* runs, const uint32_t* entries, const uint32_t* mags, const Affine<F>* src, Affine<F>* partials, Affine<F>* out) {
+  const ColsumRun r = runs[index];
+  XYZZ<F> acc = XYZZ<F>::identity();
+#pragma unroll 1
+  for (uint32_t k = 0; k < r.len; k++) {
+    Affine<F> p;
+    if (entries) {
+      const uint32_t e = entries[r.off + k];
+      p = src[e >> 1];
+      if ((e & 1u) && !aff_is_identity(p)) p.y = F::neg(p.y);
+    } else p = src[r.off + k];
+    add_mixed(acc, p);
+  }
+  Affine<F> a = to_affine(acc);
+  if (r.bits > 1) a = to_affine(pt_scalar_mul_bits(a, mags + 8 * (size_t)r.mag, (int)r.bits));
+  if (r.dst & COLSUM_FINAL) out[r.dst & ~COLSUM_FINAL] = a; else partials[r.dst] = a;
+}
+
+// out[j] = P[j + n] − P[j] for j < n − 1: the points [(tau^n − 1)·tau^j]G of the h query before 1/delta
+template <class F>
+VZ_HD void pt_diff(size_t j, size_t n, const Affine<F>* points, Affine<F>* out) {
+  Affine<F> m = points[j];
+  if (!aff_is_identity(m)) m.y = F::neg(m.y);
+  XYZZ<F> acc = from_affine(points[j + n]);
+  add_mixed(acc, m);
+  out[j] = to_affine(acc);
 }
 
 }  // namespace vz

@@ -1,7 +1,10 @@
 // Group-side kernels of a Groth16 set-up from a powers-of-tau string: what such a set-up does to POINTS where the trapdoor set-up
-// (groth16.hip) works on scalars and ends in fixed-base multiplications.  Built so far: the same-scalar multiplication that applies 1/delta to the l and
-// h queries, and the transform over points that turns the string's [tau^k]G into the Lagrange basis [L_j(tau)]G — both for G1 and for G2.  Shared by the
-// set-up to come, vimz_powers_lagrange and the test hooks (g16_powers.hip).
+// (groth16.hip) works on scalars and ends in fixed-base multiplications: the same-scalar multiplication that applies 1/delta to the l and h queries, the
+// transform over points that turns the string's [tau^k]G into the Lagrange basis [L_j(tau)]G, the column sums Σ c·L_r of the matrices over that basis (the a, b
+// and K queries) — each for G1 and for G2 — and the differences [tau^(j+n) − tau^j]G1 of the h query.  Shared by vimz_decider_setup_from_powers (groth16.hip),
+// vimz_powers_lagrange and the test hooks (g16_powers.hip).  In every kernel a thread owns its outputs, no kernel waits on another workgroup, the stream orders the
+// launches and every loop bound comes from the host; what a thread does is a host-and-device function of its index (g16_point_stage.hpp), looped on the CPU by
+// tests/native/pt_stage_check.cpp and colsum_plan_check.cpp.
 #pragma once
 #include "cyclefold_internal.hpp"
 #include "g16_point_stage.hpp"
@@ -27,3 +30,26 @@ inline size_t g16_point_transform_words(int logn) { return 8 * (((size_t)1 << lo
 // no allocation, no synchronisation.  `twiddles`: g16_point_transform_words(logn) words on the device, filled here (public values: no wiping).
 hipError_t g16_point_transform(hipStream_t s, G1Aff* points, int logn, bool inverse, bool scaled, uint32_t* twiddles);
 hipError_t g16_point_transform(hipStream_t s, G2PowAff* points, int logn, bool inverse, bool scaled, uint32_t* twiddles);
+
+// A plan of column sums (g16_colsum_plan.hpp) on the device, with room for the partials of points of `point_bytes` each: made and freed by the caller, read by
+// any number of g16_column_sums calls one after another on one stream.
+struct ColsumDevice {
+  uint32_t n_cols = 0, n_points = 0;
+  uint32_t *entries = nullptr, *mags = nullptr;
+  vz::ColsumRun* runs = nullptr;                  // the levels' runs one after another
+  struct Level { size_t first; uint32_t n_runs, n_partials; };
+  std::vector<Level> levels;
+  void* partials[2] = {nullptr, nullptr};         // level k writes partials[k & 1] and reads the other
+  size_t point_bytes = 0;
+};
+// blocking copies (the plan's vectors are pageable); any failure frees what was allocated
+hipError_t g16_colsum_upload(const vz::ColsumPlan& plan, size_t point_bytes, ColsumDevice* dev);
+void g16_colsum_free(ColsumDevice& dev);
+// Queues on `s`: out[j] = Σ_{entries of column j} c·points[row] for the plan's n_cols columns, canonical affine with the identity as zeros (the form
+// bases_from_device takes); points: at least plan.n_points affine points (Montgomery coordinates).  A memset of `out`, then one k_col_runs launch per level, one
+// thread per run; `dev` must have been uploaded for this point size.  out must not overlap points.
+hipError_t g16_column_sums(hipStream_t s, const ColsumDevice& dev, const G1Aff* points, G1Aff* out);
+hipError_t g16_column_sums(hipStream_t s, const ColsumDevice& dev, const G2PowAff* points, G2PowAff* out);
+// Queues on `s`: out[j] = dinv·(tau_g1[j + n] − tau_g1[j]) for j < n − 1 — the h query [(tau^n − 1)·tau^j / delta]G1 from the string's 2n − 1 powers: k_point_diff,
+// then k_scale_points in place.  dinv_canon: 8 canonical words on the device, wiped by the caller.  out: n − 1 points, not overlapping tau_g1.
+hipError_t g16_h_query(hipStream_t s, const G1Aff* tau_g1, size_t n, const uint32_t* dinv_canon, G1Aff* out);

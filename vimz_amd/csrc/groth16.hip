@@ -12,11 +12,13 @@
 // (synthesis, witness, its sparse products — 10^6 rows of a few terms), the QAP evaluation at the trapdoor, the final point arithmetic.
 #include <sys/random.h>
 #include <functional>
+#include <map>
 #include <thread>
 #include "cyclefold_internal.hpp"
 #include "decider_view.hpp"
 #include "aug/decider.hpp"
 #include "decider_chains.hpp"
+#include "g16_powers.hpp"
 #include "pairing.hpp"
 #include "vecops_api.hpp"
 #ifdef VIMZ_TESTING
@@ -501,29 +503,39 @@ int kzg_vk_matches_srs(vimz_cf* v, const G2PAff& vk, const char* who) {
   return VIMZ_OK;
 }
 
+// What every set-up begins with: the KZG verifying key (optional) checked against the prover's SRS, the decider circuit for the prover's shapes, the key's sizes
+// and the constants of the domain
+int decider_setup_head(vimz_cf* v, const uint64_t kzg_vk_g2[16], bool light, vimz_decider& d) {
+  vimz_ctx* ctx = v->ctx;
+  d.vk = v; d.ctx = ctx;
+  d.kzg_vk.x = d.kzg_vk.y = Fq2::zero();
+  if (kzg_vk_g2) {
+    if (!get_g2(kzg_vk_g2, &d.kzg_vk) || !vz::pairing::g2_on_curve(d.kzg_vk) || !vz::pairing::g2_in_subgroup(d.kzg_vk))
+      return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_decider_setup: the KZG verifying key is not a point of G2");
+    const int rcv = kzg_vk_matches_srs(v, d.kzg_vk, "vimz_decider_setup");
+    if (rcv) return rcv;
+  }
+  { const int rcb = decider_circuit_build(v, light, d); if (rcb) return rcb; }
+  G16Key& K = d.key;
+  const cb::BuilderT<Fe>& b = d.circ.b;
+  K.m = b.n_wires; K.n_pub = d.circ.n_public; K.n_c = b.n_constraints();
+  K.n = 1; K.logn = 0;
+  while (K.n < K.n_c + K.n_pub + 1) { K.n <<= 1; K.logn++; }
+  if (K.logn > 26) return vz_fail(ctx, VIMZ_ERR_INVALID, "decider: circuit too large for the domain");
+  if (!domain_constants(K, K.logn)) return vz_fail(ctx, VIMZ_ERR_INVALID, "decider: root of unity");
+  return VIMZ_OK;
+}
+
 int decider_setup_impl(vimz_cf* v, const uint64_t kzg_vk_g2[16], const Trapdoor& td, bool light, vimz_decider** out, double seconds[4]) {
   vimz_ctx* ctx = v->ctx;
   const double t_all = now_s();
   std::unique_ptr<vimz_decider> d(new vimz_decider());
-  d->vk = v; d->ctx = ctx;
-  d->kzg_vk.x = d->kzg_vk.y = Fq2::zero();
-  if (kzg_vk_g2) {
-    if (!get_g2(kzg_vk_g2, &d->kzg_vk) || !vz::pairing::g2_on_curve(d->kzg_vk) || !vz::pairing::g2_in_subgroup(d->kzg_vk))
-      return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_decider_setup: the KZG verifying key is not a point of G2");
-    const int rcv = kzg_vk_matches_srs(v, d->kzg_vk, "vimz_decider_setup");
-    if (rcv) return rcv;
-  }
-  { const int rcb = decider_circuit_build(v, light, *d); if (rcb) return rcb; }
+  { const int rch = decider_setup_head(v, kzg_vk_g2, light, *d); if (rch) return rch; }
   const double t_syn = now_s();
   G16Key& K = d->key;
   const cb::BuilderT<Fe>& b = d->circ.b;
-  K.m = b.n_wires; K.n_pub = d->circ.n_public; K.n_c = b.n_constraints();
-  K.n = 1; K.logn = 0;
-  while (K.n < K.n_c + K.n_pub + 1) { K.n <<= 1; K.logn++; }
-  if (K.logn > 26) return vz_fail(ctx, VIMZ_ERR_INVALID, "decider: circuit too large for the domain");
   const Fe tau = td.tau, alpha = td.alpha, beta = td.beta, gamma = td.gamma, delta = td.delta;
   const Fe gamma_inv = Fe::pow_pm2(gamma), delta_inv = Fe::pow_pm2(delta);
-  if (!domain_constants(K, K.logn)) return vz_fail(ctx, VIMZ_ERR_INVALID, "decider: root of unity");
   // Lagrange basis at tau: L_j(tau) = Z(tau)/n · ω^j / (tau − ω^j)   (batch inversion)
   const Fe z_tau = Fe::sub(fr_pow_u64(tau, K.n), Fe::one());
   if (z_tau.is_zero()) return vz_fail(ctx, VIMZ_ERR_INVALID, "decider: tau lies in the domain");
@@ -612,6 +624,177 @@ int decider_setup_impl(vimz_cf* v, const uint64_t kzg_vk_g2[16], const Trapdoor&
   const double t_end = now_s();
   d->setup_s[0] = t_syn - t_all; d->setup_s[1] = t_qap - t_syn; d->setup_s[2] = t_end - t_qap; d->setup_s[3] = t_end - t_all;
   if (seconds) memcpy(seconds, d->setup_s, sizeof(d->setup_s));
+  *out = d.release();
+  return VIMZ_OK;
+}
+
+// ---- the set-up from a powers-of-tau string: the key by GROUP operations on the string's points — tau, alpha and beta are never in this
+// process, gamma = 1, and delta is the only secret drawn here.  tests/_g16_powers_ref.derive_key states the derivation on scalars. ------------------------------
+struct PowersString { const uint64_t* tau_g1; size_t n_tau_g1; const uint64_t *tau_g2, *alpha_g1, *beta_g1; size_t n_pow; const uint64_t* beta_g2; int form; };
+
+void host_parallel(uint64_t n, const std::function<void(uint64_t, uint64_t)>& f) {
+  const unsigned TH = std::max(1u, std::min(16u, usable_cpus()));
+  std::vector<std::thread> th;
+  for (unsigned t = 0; t < TH; t++) { const uint64_t lo = n * t / TH, hi = n * (t + 1) / TH; if (lo < hi) th.emplace_back([&f, lo, hi] { f(lo, hi); }); }
+  for (auto& x : th) x.join();
+}
+bool string_point_on_curve(const G1Aff& p) { return vz::pairing::g1_on_curve(p); }
+bool string_point_on_curve(const G2PAff& p) { return vz::pairing::g2_on_curve(p); }
+// n points of a string as words (form = VIMZ_FORM_*) -> Montgomery coordinates.  0: fine; 1: a coordinate is not below q; 2: a point is not on its curve
+template <class A>
+int string_points_in(const uint64_t* words, size_t n, int form, A* out) {
+  const size_t per = sizeof(A) / sizeof(Fq);
+  std::atomic<int> bad{0};
+  host_parallel(n, [&](uint64_t lo, uint64_t hi) {
+    for (uint64_t i = lo; i < hi; i++) {
+      Fq* c = (Fq*)(out + i);
+      for (size_t k = 0; k < per; k++) {
+        Fq x; memcpy(x.v, words + 4 * (per * i + k), 32);
+        if (!x.is_reduced()) { bad.store(1); return; }
+        c[k] = form == VIMZ_FORM_MONTGOMERY ? x : Fq::to_mont(x);
+      }
+      if (!string_point_on_curve(out[i])) { int z = 0; bad.compare_exchange_strong(z, 2); return; }
+    }
+  });
+  return bad.load();
+}
+
+// delta_given: the test hook's; NULL: drawn from the OS.  seconds (optional) = {synthesis, checks + upload, transforms, column sums, l/h scaling + key tables, total}
+int decider_setup_powers_impl(vimz_cf* v, bool light, const PowersString& S, const Fe* delta_given, vimz_decider** out, double seconds[6]) {
+  vimz_ctx* ctx = v->ctx;
+  auto bad = [&](const char* m) { return vz_fail(ctx, VIMZ_ERR_INVALID, (std::string("vimz_decider_setup_from_powers: ") + m).c_str()); };
+  const double t_all = now_s();
+  std::unique_ptr<vimz_decider> d(new vimz_decider());
+  { const int rch = decider_setup_head(v, nullptr, light, *d); if (rch) return rch; }
+  const double t_syn = now_s();
+  G16Key& K = d->key;
+  const cb::BuilderT<Fe>& b = d->circ.b;
+  const size_t n = K.n, m = K.m, n_l = m - K.n_pub - 1;
+  if (K.logn < 1) return bad("the circuit's domain is a single point");
+  if (S.n_pow < n || S.n_tau_g1 < 2 * n - 1) return bad("the string is shorter than the circuit's domain: n powers are needed, and 2n - 1 of tau in G1");
+  // the string's points: beta·tau^k, alpha·tau^k and tau^k side by side (the K query sums over all three), the 2n − 1 powers for h, and G2's
+  std::vector<G1Aff> lag(3 * n), tau(2 * n - 1); std::vector<G2PAff> tau2(n); G2PAff beta2;
+  { const struct { const uint64_t* w; size_t n; G1Aff* dst; } g1s[3] = {{S.beta_g1, n, lag.data()}, {S.alpha_g1, n, lag.data() + n}, {S.tau_g1, 2 * n - 1, tau.data()}};
+    int rc = 0;
+    for (const auto& a : g1s) if (!rc) rc = string_points_in<G1Aff>(a.w, a.n, S.form, a.dst);
+    if (!rc) rc = string_points_in<G2PAff>(S.tau_g2, n, S.form, tau2.data());
+    if (!rc) rc = string_points_in<G2PAff>(S.beta_g2, 1, S.form, &beta2);
+    if (rc) return bad(rc == 1 ? "a coordinate is not below the modulus" : "a point is not on its curve"); }
+  memcpy(lag.data() + 2 * n, tau.data(), sizeof(G1Aff) * n);
+  const G1Aff g1 = g1_generator(); const G2PAff g2 = g2_generator();
+  G1Aff ng = g1; ng.y = Fq::neg(g1.y);
+  auto same2 = [](const G2PAff& p, const G2PAff& q) { return p.x.c0.eq(q.x.c0) && p.x.c1.eq(q.x.c1) && p.y.c0.eq(q.y.c0) && p.y.c1.eq(q.y.c1); };
+  if (!vz::pairing::consts().ok) return bad("pairing constants");
+  if (!tau[0].x.eq(g1.x) || !tau[0].y.eq(g1.y)) return bad("tau_g1[0] is not the generator of G1");
+  if (!same2(tau2[0], g2)) return bad("tau_g2[0] is not the generator of G2");
+  if (aff_is_identity(tau[1]) || aff_is_identity(lag[0]) || aff_is_identity(lag[n]) || aff_is_identity(tau2[1]) || aff_is_identity(beta2)) return bad("tau, alpha or beta is zero: a point of the string is the identity");
+  if (!vz::pairing::g2_in_subgroup(beta2)) return bad("beta_g2 is not in the subgroup");
+  if (!vz::pairing::g2_in_subgroup(tau2[1])) return bad("tau_g2[1] is not in the subgroup");
+  if (!vz::pairing::product_is_one({{tau[1], g2}, {ng, tau2[1]}})) return bad("tau_g1[1] and tau_g2[1] are not of one tau");
+  if (!vz::pairing::product_is_one({{lag[0], g2}, {ng, beta2}})) return bad("beta_g1[0] and beta_g2 are not of one beta");
+  d->kzg_vk = tau2[1];
+  { const int rcv = kzg_vk_matches_srs(v, d->kzg_vk, "vimz_decider_setup_from_powers"); if (rcv) return rcv; }
+  // delta: this party's only secret
+  struct Secret { Fe delta, dinv_canon; ~Secret() { wipe(this, sizeof(*this)); } } sec;
+  if (delta_given) sec.delta = *delta_given; else if (!fr_random(&sec.delta)) return bad("no randomness from the OS");
+  if (sec.delta.is_zero()) return bad("delta is zero");
+  sec.dinv_canon = Fe::from_mont(Fe::pow_pm2(sec.delta));
+
+  std::lock_guard<std::mutex> g(ctx->mu);
+  P_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  struct Dev {
+    G1Aff *lag = nullptr, *tau = nullptr, *a = nullptr, *b1 = nullptr, *k = nullptr, *h = nullptr; G2PAff *l2 = nullptr, *b2 = nullptr; uint32_t *tw = nullptr, *dinv = nullptr;
+    ColsumDevice plan;
+    void drop(void* p) { if (p) hipFree(p); }
+    ~Dev() { if (dinv) { hipMemset(dinv, 0, 32); }      // (an error path between 1/delta's upload and its wipe ends here: the device copy never outlives the call unwiped)
+             for (void* p : {(void*)lag, (void*)tau, (void*)a, (void*)b1, (void*)k, (void*)h, (void*)l2, (void*)b2, (void*)tw, (void*)dinv}) drop(p); g16_colsum_free(plan); }
+  } D;
+  P_TRY(hipMalloc((void**)&D.lag, sizeof(G1Aff) * 3 * n)); P_TRY(hipMalloc((void**)&D.tau, sizeof(G1Aff) * (2 * n - 1))); P_TRY(hipMalloc((void**)&D.l2, sizeof(G2PAff) * n));
+  P_TRY(hipMalloc((void**)&D.tw, 4 * g16_point_transform_words(K.logn)));
+  P_TRY(hipMemcpy(D.lag, lag.data(), sizeof(G1Aff) * 3 * n, hipMemcpyHostToDevice)); P_TRY(hipMemcpy(D.tau, tau.data(), sizeof(G1Aff) * (2 * n - 1), hipMemcpyHostToDevice));
+  P_TRY(hipMemcpy(D.l2, tau2.data(), sizeof(G2PAff) * n, hipMemcpyHostToDevice));
+  const double t_up = now_s();
+  // the four Lagrange bases: beta·L, alpha·L, L in G1, L in G2 (one table of twiddles serves all: the stream orders them)
+  for (int q = 0; q < 3; q++) P_TRY(g16_point_transform(s, D.lag + q * n, K.logn, true, true, D.tw));
+  P_TRY(g16_point_transform(s, D.l2, K.logn, true, true, D.tw));
+  // ... under which the host plans the column sums
+  std::vector<uint32_t> dict(8 * b.dict.size());
+  for (size_t i = 0; i < b.dict.size(); i++) { const Fe c = Fe::from_mont(b.dict[i]); memcpy(&dict[8 * i], c.v, 32); }
+  const cb::Csr* Ms[3] = {&b.A, &b.B, &b.C};
+  for (const cb::Csr* M : Ms) if (M->row_ptr.size() != (size_t)K.n_c + 1) return bad("a matrix does not have one row a constraint");
+  std::vector<ColsumUnit> units(K.n_pub + 1);
+  for (uint32_t i = 0; i <= K.n_pub; i++) units[i] = {K.n_c + i, i};
+  auto part = [&](int q, uint32_t base) { return ColsumPart{Ms[q]->row_ptr.data(), Ms[q]->col.data(), Ms[q]->coef.data(), K.n_c, base}; };
+  ColsumPlan plan_a, plan_b, plan_k; std::string err;
+  { const ColsumPart pa = part(0, 0), pb = part(1, 0), pk[3] = {part(0, 0), part(1, (uint32_t)n), part(2, (uint32_t)(2 * n))};
+    if (!colsum_plan(&pa, 1, units.data(), units.size(), dict.data(), b.dict.size(), BnFr::MOD.w, K.m, (uint32_t)n, &plan_a, &err) ||
+        !colsum_plan(&pb, 1, nullptr, 0, dict.data(), b.dict.size(), BnFr::MOD.w, K.m, (uint32_t)n, &plan_b, &err) ||
+        !colsum_plan(pk, 3, units.data(), units.size(), dict.data(), b.dict.size(), BnFr::MOD.w, K.m, (uint32_t)(3 * n), &plan_k, &err)) return bad(err.c_str()); }
+  P_TRY(hipStreamSynchronize(s));
+  const double t_tr = now_s();
+  // VIMZ_DECIDER_POWERS_STATS (read per call): the plans' shapes and the set-up's device memory on stderr, for profiles/decider_powers.txt
+  const bool stats = getenv("VIMZ_DECIDER_POWERS_STATS") != nullptr;
+  size_t free_start = 0, free_min = 0, mem_total = 0;
+  auto sample = [&] { size_t f = 0; if (stats && hipMemGetInfo(&f, &mem_total) == hipSuccess) { if (!free_start) free_start = free_min = f; free_min = std::min(free_min, f); } };
+  sample();
+  if (stats) for (const auto& pl : {std::make_pair("a", &plan_a), std::make_pair("b", &plan_b), std::make_pair("K", &plan_k)}) {
+    fprintf(stderr, "decider from powers: plan %s: %zu entries, %zu magnitudes, runs per level", pl.first, pl.second->entries.size(), pl.second->mags.size() / 8);
+    for (const ColsumLevel& lv : pl.second->levels) fprintf(stderr, " %zu", lv.runs.size());
+    fprintf(stderr, "; most level-0 runs of a column %u; level-0 runs by bitlen(|c|):", pl.second->max_col_runs);
+    std::map<uint32_t, size_t> hist;
+    for (const ColsumRun& r : pl.second->levels[0].runs) hist[r.bits]++;
+    for (const auto& h : hist) fprintf(stderr, " %u:%zu", h.first, h.second);
+    fputc('\n', stderr);
+  }
+  // the queries: a = colsum(A, L) + units, b = colsum(B, L) in both groups, K = colsum(A, beta·L) + colsum(B, alpha·L) + colsum(C, L) + units over beta·L
+  auto sums = [&](const ColsumPlan& plan, auto* points, auto** dst) -> int {
+    typedef typename std::remove_pointer<typename std::remove_pointer<decltype(dst)>::type>::type A;
+    P_TRY(g16_colsum_upload(plan, sizeof(A), &D.plan));
+    P_TRY(hipMalloc((void**)dst, sizeof(A) * m));
+    P_TRY(g16_column_sums(s, D.plan, (const A*)points, *dst));
+    sample();
+    P_TRY(hipStreamSynchronize(s));
+    g16_colsum_free(D.plan);
+    return VIMZ_OK;
+  };
+  int rc;
+  if ((rc = sums(plan_k, D.lag, &D.k)) || (rc = sums(plan_a, D.lag + 2 * n, &D.a)) || (rc = sums(plan_b, D.lag + 2 * n, &D.b1)) || (rc = sums(plan_b, D.l2, &D.b2))) return rc;
+  const double t_cs = now_s();
+  // l = K[n_pub + 1 ..]/delta in place, h = (tau^(j+n) − tau^j)/delta; ic = K[.. n_pub] (gamma = 1)
+  P_TRY(hipMalloc((void**)&D.dinv, 32)); P_TRY(hipMalloc((void**)&D.h, sizeof(G1Aff) * std::max<size_t>(n - 1, 1)));
+  P_TRY(hipMemcpy(D.dinv, sec.dinv_canon.v, 32, hipMemcpyHostToDevice));
+  P_TRY(g16_scale_points(s, D.k + K.n_pub + 1, n_l, D.dinv, D.k + K.n_pub + 1));
+  P_TRY(g16_h_query(s, D.tau, n, D.dinv, D.h));
+  sample();
+  P_TRY(hipMemsetAsync(D.dinv, 0, 32, s));
+  K.ic.resize(K.n_pub + 1);
+  P_TRY(hipMemcpyAsync(K.ic.data(), D.k, sizeof(G1Aff) * (K.n_pub + 1), hipMemcpyDeviceToHost, s));
+  std::vector<G2PAff> b2(m);
+  P_TRY(hipMemcpyAsync(b2.data(), D.b2, sizeof(G2PAff) * m, hipMemcpyDeviceToHost, s));
+  P_TRY(hipStreamSynchronize(s));
+  // the bases and the full G2 query go before the key's tables come
+  for (void** p : {(void**)&D.lag, (void**)&D.tau, (void**)&D.l2, (void**)&D.b2, (void**)&D.tw, (void**)&D.dinv}) { hipFree(*p); *p = nullptr; }
+  const struct { G1Aff** pts; size_t off, n; vimz_bases** q; } qs[4] = {{&D.a, 0, m, &K.a_q}, {&D.b1, 0, m, &K.b1_q}, {&D.k, (size_t)K.n_pub + 1, n_l, &K.l_q}, {&D.h, 0, n - 1, &K.h_q}};
+  for (const auto& q : qs) {
+    if ((rc = bases_from_device(ctx, *q.pts + q.off, q.n, q.q))) return rc;
+    hipFree(*q.pts); *q.pts = nullptr;
+  }
+  { // the G2 query holds only the wires whose point is not the identity
+    std::vector<uint32_t> ix; std::vector<G2PAff> pts;
+    for (uint32_t i = 0; i < K.m; i++) if (!aff_is_identity(b2[i])) { ix.push_back(i); pts.push_back(b2[i]); }
+    K.n_b2 = (uint32_t)ix.size();
+    P_TRY(hipMalloc((void**)&K.b2_q, sizeof(G2PAff) * std::max<size_t>(ix.size(), 1))); P_TRY(hipMalloc((void**)&K.b2_idx, 4 * std::max<size_t>(ix.size(), 1)));
+    P_TRY(hipMemcpy(K.b2_q, pts.data(), sizeof(G2PAff) * pts.size(), hipMemcpyHostToDevice)); P_TRY(hipMemcpy(K.b2_idx, ix.data(), 4 * ix.size(), hipMemcpyHostToDevice)); }
+  if ((rc = domain_tables(ctx, s, K))) return rc;
+  sample();
+  if (stats) fprintf(stderr, "decider from powers: device memory of the set-up at its peak %.1f MB above what was in use before the column sums (the four bases, the string's tau_g1 and the twiddles: %.1f MB), %.1f MB of %.1f MB free at the lowest\n",
+                     (free_start - free_min) / 1048576.0, (sizeof(G1Aff) * (5 * n - 1) + sizeof(G2PAff) * n + 4 * g16_point_transform_words(K.logn)) / 1048576.0, free_min / 1048576.0, mem_total / 1048576.0);
+  K.alpha1 = lag[n]; K.beta1 = lag[0]; K.beta2 = beta2; K.gamma2 = g2;
+  K.delta1 = to_affine(host_mul_fr<Fq>(g1, sec.delta)); K.delta2 = to_affine(host_mul_fr<Fq2>(g2, sec.delta));
+  const double t_end = now_s();
+  d->setup_s[0] = t_syn - t_all; d->setup_s[1] = t_up - t_syn; d->setup_s[2] = t_end - t_up; d->setup_s[3] = t_end - t_all;
+  if (seconds) { seconds[0] = t_syn - t_all; seconds[1] = t_up - t_syn; seconds[2] = t_tr - t_up; seconds[3] = t_cs - t_tr; seconds[4] = t_end - t_cs; seconds[5] = t_end - t_all; }
   *out = d.release();
   return VIMZ_OK;
 }
@@ -733,6 +916,16 @@ int vimz_decider_setup(vimz_cf* v, const uint64_t kzg_vk_g2[16], int light, vimz
   Trapdoor t;
   if (!trapdoor_random(t)) return vz_fail(v->ctx, VIMZ_ERR_INVALID, "vimz_decider_setup: no randomness from the OS");
   return decider_setup_impl(v, kzg_vk_g2, t, light != 0, out, seconds);
+}
+// The same from a powers-of-tau string (iden3.read_ptau's arrays; form = VIMZ_FORM_* of the coordinates): tau, alpha and beta are the string's and never in this
+// process, gamma = 1, delta is drawn here from the OS and wiped.  The KZG verifying key is the string's tau_g2[1]: the prover's ck_main must be the SRS of the same
+// string (hip.kzg_from_powers).  Refusals and what stays unjudged: include/vimz_hip.h.
+int vimz_decider_setup_from_powers(vimz_cf* v, int light, const uint64_t* tau_g1, size_t n_tau_g1, const uint64_t* tau_g2, const uint64_t* alpha_g1, const uint64_t* beta_g1, size_t n_pow,
+                                   const uint64_t beta_g2[16], int form, vimz_decider** out, double seconds[6]) {
+  if (!v) return VIMZ_ERR_INVALID;
+  if (!out || !tau_g1 || !tau_g2 || !alpha_g1 || !beta_g1 || !beta_g2) return vz_fail(v->ctx, VIMZ_ERR_INVALID, "vimz_decider_setup_from_powers: NULL argument");
+  if (form != VIMZ_FORM_CANONICAL && form != VIMZ_FORM_MONTGOMERY) return vz_fail(v->ctx, VIMZ_ERR_INVALID, "vimz_decider_setup_from_powers: form is VIMZ_FORM_*");
+  return decider_setup_powers_impl(v, light != 0, PowersString{tau_g1, n_tau_g1, tau_g2, alpha_g1, beta_g1, n_pow, beta_g2, form}, nullptr, out, seconds);
 }
 #ifdef VIMZ_TESTING
 // Host only, no GPU: the decider circuit (aug/decider.hpp) over the Nova + CycleFold recursion of the trivial step circuit with made-up commitments — the
@@ -916,6 +1109,24 @@ int vimz_testing_kzg_setup_seeded(vimz_ctx* ctx, const uint8_t* seed, size_t see
 int vimz_testing_decider_setup_seeded(vimz_cf* v, const uint64_t kzg_vk_g2[16], int light, const uint8_t* seed, size_t seed_len, vimz_decider** out, double seconds[4]) {
   if (!v || !out || (!seed && seed_len)) return VIMZ_ERR_INVALID;
   return decider_setup_impl(v, kzg_vk_g2, trapdoor_seeded(seed, seed_len), light != 0, out, seconds);
+}
+// the trapdoor set-up with a GIVEN trapdoor (tau, alpha, beta, gamma, delta: 4 canonical words each, non-zero), and the set-up from a string with a given delta:
+// what tests/test_gpu_decider_from_powers.py compares byte for byte
+int vimz_testing_decider_setup_trapdoor(vimz_cf* v, const uint64_t kzg_vk_g2[16], int light, const uint64_t td[20], vimz_decider** out, double seconds[4]) {
+  if (!v || !out || !td) return VIMZ_ERR_INVALID;
+  Trapdoor t; Fe* dst[5] = {&t.tau, &t.alpha, &t.beta, &t.gamma, &t.delta};
+  for (int k = 0; k < 5; k++) { Fe c; memcpy(c.v, td + 4 * k, 32); if (!c.is_reduced() || c.is_zero()) return vz_fail(v->ctx, VIMZ_ERR_INVALID, "vimz_testing_decider_setup_trapdoor: a scalar is zero or not below the modulus"); *dst[k] = Fe::to_mont(c); }
+  return decider_setup_impl(v, kzg_vk_g2, t, light != 0, out, seconds);
+}
+int vimz_testing_decider_setup_from_powers_delta(vimz_cf* v, int light, const uint64_t* tau_g1, size_t n_tau_g1, const uint64_t* tau_g2, const uint64_t* alpha_g1, const uint64_t* beta_g1,
+                                                 size_t n_pow, const uint64_t beta_g2[16], int form, const uint64_t delta[4], vimz_decider** out, double seconds[6]) {
+  if (!v) return VIMZ_ERR_INVALID;
+  if (!out || !tau_g1 || !tau_g2 || !alpha_g1 || !beta_g1 || !beta_g2 || !delta || (form != VIMZ_FORM_CANONICAL && form != VIMZ_FORM_MONTGOMERY))
+    return vz_fail(v->ctx, VIMZ_ERR_INVALID, "vimz_testing_decider_setup_from_powers_delta: bad argument");
+  Fe c; memcpy(c.v, delta, 32);
+  if (!c.is_reduced() || c.is_zero()) return vz_fail(v->ctx, VIMZ_ERR_INVALID, "vimz_testing_decider_setup_from_powers_delta: delta is zero or not below the modulus");
+  const Fe dm = Fe::to_mont(c);
+  return decider_setup_powers_impl(v, light != 0, PowersString{tau_g1, n_tau_g1, tau_g2, alpha_g1, beta_g1, n_pow, beta_g2, form}, &dm, out, seconds);
 }
 // ---- the decider's kernels on a caller's shapes (tests/test_gpu_g16_kernels.py): the functions the set-up and the prover call, over made-up inputs ----------
 }  // extern "C"

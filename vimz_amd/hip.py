@@ -957,10 +957,18 @@ class Decider:
     contracts/*Verifier.sol and their local verification.  prover: a CycleFoldIVC (shapes, keys, context; keep it open); kzg_vk: [tau]G2 of the SRS
     its ck_main is made of (kzg_setup), or None (no verify).  light=False: the FULL decider (decider.rs:13-21: the running CycleFold instance's commitments
     and relation are checked inside the circuit); light=True: the reference's opt-in `light-test` variant (vimz/Cargo.toml:56-59).  The Groth16 trapdoor is drawn from the OS's randomness and forgotten; `seed` selects
-    the deterministic TEST setup of libvimz_hip_testing.so."""
+    the deterministic TEST setup of libvimz_hip_testing.so.
+    powers: iden3.read_ptau's dictionary instead — vimz_decider_setup_from_powers: the key is derived on the GPU from the string's points, so tau, alpha and beta
+    are the string's and never in this process, gamma = 1, and only delta is drawn here (and forgotten).  kzg_vk is then the string's tau_g2[1] — passing one as
+    well is refused — and the prover's ck_main must come from the same string (kzg_from_powers).  `delta` (an int; with powers only) selects the TEST set-up of
+    libvimz_hip_testing.so with that delta."""
     RESULT_BITS = {1: "fewer than two steps", 2: "KZG opening of cmW", 4: "KZG opening of cmE", 8: "Groth16", 16: "a word pair is not a curve point"}
 
-    def __init__(self, prover, kzg_vk=None, seed=None, light=False):
+    def __init__(self, prover, kzg_vk=None, seed=None, light=False, powers=None, delta=None):
+        if powers is not None and (kzg_vk is not None or seed is not None):
+            raise L.VimzError(L.ERR_INVALID, "Decider: powers= brings its own KZG verifying key (the string's tau_g2[1]) and draws no trapdoor: pass neither kzg_vk= nor seed= with it")
+        if delta is not None and powers is None:
+            raise L.VimzError(L.ERR_INVALID, "Decider: delta= goes with powers= only")
         self.prover, self.ctx = prover, prover.ctx
         self.light = bool(light)
         lib = self.ctx.lib
@@ -973,6 +981,9 @@ class Decider:
         lib.vimz_decider_vk.restype = C.c_int64
         lib.vimz_decider_prove.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_double)]
         lib.vimz_decider_verify.argtypes = [vp, C.c_uint64, vp, vp, vp, C.POINTER(C.c_uint32)]
+        if powers is not None:
+            self._setup_from_powers(powers, delta)
+            return
         h = vp()
         sec = (C.c_double * 4)()
         self._kzg_vk = None if kzg_vk is None else np.ascontiguousarray(kzg_vk, dtype=np.uint64)
@@ -985,6 +996,29 @@ class Decider:
             self.ctx._chk(fn(prover.h, kp, int(self.light), bytes(seed), len(seed), C.byref(h), sec))
         self.h = h
         self.setup_seconds = {"circuit_synthesis": sec[0], "qap_at_trapdoor_host": sec[1], "key_points_gpu": sec[2], "total": sec[3]}
+
+    def _setup_from_powers(self, powers, delta):
+        lib, vp = self.ctx.lib, C.c_void_p
+        a = {name: np.ascontiguousarray(powers[name], dtype=np.uint64).reshape(-1, 8 * group) for name, group in _LAGRANGE_ARRAYS + (("beta_g2", 2),)}
+        n_pow = min(a["tau_g2"].shape[0], a["alpha_g1"].shape[0], a["beta_g1"].shape[0])
+        if a["beta_g2"].shape[0] < 1:
+            raise L.VimzError(L.ERR_INVALID, "Decider: the string has no beta_g2")
+        head = [self.prover.h, int(self.light), _ptr(a["tau_g1"]), a["tau_g1"].shape[0], _ptr(a["tau_g2"]), _ptr(a["alpha_g1"]), _ptr(a["beta_g1"]), n_pow, _ptr(a["beta_g2"]), L.FORM_MONTGOMERY]
+        types = [vp, C.c_int, vp, C.c_size_t, vp, vp, vp, C.c_size_t, vp, C.c_int]
+        h = vp()
+        sec = (C.c_double * 6)()
+        if delta is None:
+            lib.vimz_decider_setup_from_powers.argtypes = types + [C.POINTER(vp), C.POINTER(C.c_double)]
+            self.ctx._chk(lib.vimz_decider_setup_from_powers(*head, C.byref(h), sec))
+        else:
+            fn = _seeded(self.ctx, "vimz_testing_decider_setup_from_powers_delta")
+            fn.argtypes = types + [vp, C.POINTER(vp), C.POINTER(C.c_double)]
+            dw = np.frombuffer(int(delta).to_bytes(32, "little"), dtype="<u8").astype(np.uint64)
+            self.ctx._chk(fn(*head, _ptr(dw), C.byref(h), sec))
+        self.h = h
+        self._kzg_vk = None      # (the library holds the string's tau_g2[1]; key_words() has it)
+        self.setup_seconds = {"circuit_synthesis": sec[0], "checks_and_upload": sec[1], "transforms_gpu": sec[2], "column_sums_gpu": sec[3], "scaling_and_key_tables": sec[4],
+                              "total": sec[5]}
 
     def close(self):
         if self.h:

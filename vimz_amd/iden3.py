@@ -131,11 +131,49 @@ def split_witness(r1cs, wtns_values):
     return v[1 + n_pub:], X
 
 
+def _decider_key(argv):
+    """decider-key FILE.ptau TRANSFORMATION RESOLUTION OUT.key [--light]: the decider's Groth16 key pair for that step circuit, derived from the string on GPU 0
+    (hip.Decider(powers=): tau, alpha, beta are the string's, delta is drawn here and forgotten), as vimz_decider_key_save's bytes."""
+    light = "--light" in argv
+    args = [a for a in argv if a != "--light"]
+    if len(args) != 5 or any(a.startswith("--") for a in args):
+        print(USAGE, file=sys.stderr)
+        return 2
+    from . import folding, hip
+    with open(args[1], "rb") as fp:
+        powers = read_ptau(fp.read())
+    ctx = hip.Context(0)
+    try:
+        circuit, params = folding.prepare_folding(ctx, args[2], args[3], window_tables=0, backend="sonobe", powers=powers)
+        cf = hip.CycleFoldIVC(ctx, circuit, params.ck, params.secondary_key(), max_batch=1)
+        try:
+            dec = params.decider(cf, light=light)
+            try:
+                blob, info, sec = dec.save_key(), dec.info(), dec.setup_seconds
+            finally:
+                dec.close()
+        finally:
+            cf.close(); params.free()
+    finally:
+        ctx.close()
+    with open(args[4], "wb") as fp:
+        blob.tofile(fp)
+    print(f"decider-key: {'light' if light else 'full'} decider of {args[2]} {args[3]}, domain {info['domain']}, {blob.size} bytes -> {args[4]} (set-up {sec['total']:.1f} s)")
+    return 0
+
+
+USAGE = ("usage: python -m vimz_amd.iden3 lagrange FILE.ptau LOGN OUT.npz\n"
+         "       python -m vimz_amd.iden3 decider-key FILE.ptau TRANSFORMATION RESOLUTION OUT.key [--light]")
+
+
 def _main(argv):
     """python -m vimz_amd.iden3 lagrange FILE.ptau LOGN OUT.npz: the string's Lagrange bases over the domain of 2^LOGN points (hip.lagrange_from_powers, on GPU 0)
-    as an .npz of tau_g1, alpha_g1, beta_g1 (n, 8) and tau_g2 (n, 16) in the file's Montgomery form, with logn."""
+    as an .npz of tau_g1, alpha_g1, beta_g1 (n, 8) and tau_g2 (n, 16) in the file's Montgomery form, with logn.
+    python -m vimz_amd.iden3 decider-key ...: _decider_key."""
+    if argv and argv[0] == "decider-key":
+        return _decider_key(argv)
     if len(argv) != 4 or argv[0] != "lagrange":
-        print("usage: python -m vimz_amd.iden3 lagrange FILE.ptau LOGN OUT.npz", file=sys.stderr)
+        print(USAGE, file=sys.stderr)
         return 2
     from . import hip
     with open(argv[1], "rb") as fp:
