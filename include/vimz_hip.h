@@ -516,10 +516,35 @@ int vimz_kzg_setup(vimz_ctx* ctx, size_t n, vimz_bases** srs_out, uint64_t vk_g2
  * is zeros on both sides.  The inverse transform over points runs on the GPU (radix 2, one launch per stage, logn·n/2 scalar multiplications), on the
  * context's stream and under the context's lock like every call on a context: it does not overlap a fold on the same context (a set-up that must run under a
  * fold needs a stream of its own).  VIMZ_ERR_INVALID: a NULL pointer, a group other than 1 or 2, logn outside 1..26, n_points < 2^logn, a coordinate not below
- * q, a point not on its curve.  NOT judged: membership of the order-r subgroup of G2, and that the points are the powers of one tau (the same-ratio check of
- * the string) — the caller vouches for the string.  seconds (optional) = {host conversion and checks, device (upload, transform, download)}. */
+ * q, a point not on its curve.  Membership of the order-r subgroup of G2 and that the points are the powers of one tau (the same-ratio check of the string) are
+ * judged by vimz_powers_verify, which is opt-in: this call does not run it.  seconds (optional) = {host conversion and checks, device (upload, transform, download)}. */
 int vimz_powers_lagrange(vimz_ctx* ctx, int group /* 1: G1, 8 words a point; 2: G2, 16 words: x.c0 x.c1 y.c0 y.c1 */, const uint64_t* points, size_t n_points,
                          int form, int logn, uint64_t* out, double seconds[2]);
+/* Judges a powers-of-tau string before a set-up trusts it — what snarkjs's `powersoftau verify` does to a ceremony's file, for the arrays vimz_decider_setup_from_powers,
+ * vimz_powers_lagrange and hip.kzg_from_powers read (same layout and form): tau_g1 n_tau_g1 points, tau_g2, alpha_g1, beta_g1 n_pow points each, beta_g2 one.  On the GPU:
+ * every point is on its curve and not the identity, every point of G2 is killed by r (decided point by point: the twist's cofactor has small factors a sum would
+ * miss), and per array two random combinations S = sum rho_i·P_i, S' = sum rho_i·P_(i+1) over the pairs of neighbours, rho_i of 128 bits from the OS, wiped after use.  On
+ * the host six pairing equations: e(S', G2) = e(S, tau_g2[1]) for tau_g1, alpha_g1, beta_g1; e(G1, S') = e(tau_g1[1], S) for tau_g2 — each array is the powers of the ONE
+ * tau of tau_g2[1] up to a factor, wrongly accepted with probability at most 2^-128 —; e(tau_g1[1], G2) = e(G1, tau_g2[1]); e(beta_g1[0], G2) = e(G1, beta_g2); and the
+ * first points of tau_g1 and tau_g2 are the generators.  A stage runs only when the ones before it found nothing.
+ * Returns VIMZ_OK whenever the string was judged: a bad string is a verdict, not an error.  *result = 0: accepted; otherwise VIMZ_POWERS_* bits.  first_bad = {array: 1
+ * tau_g1, 2 tau_g2, 3 alpha_g1, 4 beta_g1, 5 beta_g2; index} of the first per-point finding (VIMZ_POWERS_COORD .. _FIRST) of the first array that has one — *result then holds
+ * that array's findings alone —, {0, 0} when there is none: a ratio that fails names its array by its bit only.  seconds (optional) = {host conversion, per-point flags
+ * (upload included), combinations, pairings}.  VIMZ_ERR_INVALID: a NULL pointer (seconds apart), n_pow < 2, n_tau_g1 < n_pow, an unknown form.  Runs on the context's stream
+ * under the context's lock, one array on the device at a time: the peak device memory is one array, its flags and the scalars (16 bytes a pair of tau_g1). */
+#define VIMZ_POWERS_COORD 0x1u           /* a coordinate is not below q */
+#define VIMZ_POWERS_OFF_CURVE 0x2u       /* a point is not on its curve */
+#define VIMZ_POWERS_IDENTITY 0x4u        /* a point is the identity */
+#define VIMZ_POWERS_SUBGROUP 0x8u        /* a point of G2 is outside the subgroup of order r */
+#define VIMZ_POWERS_FIRST 0x10u          /* tau_g1[0] or tau_g2[0] is not the generator */
+#define VIMZ_POWERS_RATIO_TAU_G1 0x20u   /* tau_g1 is not the powers of tau_g2[1]'s tau */
+#define VIMZ_POWERS_RATIO_ALPHA_G1 0x40u
+#define VIMZ_POWERS_RATIO_BETA_G1 0x80u
+#define VIMZ_POWERS_RATIO_TAU_G2 0x100u  /* tau_g2 is not the powers of tau_g1[1]'s tau */
+#define VIMZ_POWERS_HALVES 0x200u        /* tau_g1[1] and tau_g2[1] are not of one tau */
+#define VIMZ_POWERS_BETA 0x400u          /* beta_g1[0] and beta_g2 are not of one beta */
+int vimz_powers_verify(vimz_ctx* ctx, const uint64_t* tau_g1, size_t n_tau_g1, const uint64_t* tau_g2, const uint64_t* alpha_g1, const uint64_t* beta_g1, size_t n_pow,
+                       const uint64_t beta_g2[16], int form, uint32_t* result, uint64_t first_bad[2], double seconds[4]);
 /* Decider::preprocess.  prover: supplies shapes, keys and context (must outlive the object).  kzg_vk_g2 (optional): [tau]G2 of the SRS the prover's
  * ck_main is made of (needed by vimz_decider_verify; part of vimz_decider_vk; checked against that SRS: e(srs[1], G2) = e(G1, [tau]G2)).
  * light: 0 = the full decider (the reference's default), non-zero = the `light-test` variant.  The full decider bakes the first generators of the
@@ -534,12 +559,15 @@ int vimz_decider_setup(vimz_cf* prover, const uint64_t kzg_vk_g2[16], int light,
  * delta comes from the OS's randomness and is wiped after use: the key's trust rests on the string plus this one local delta.  The KZG verifying key is the
  * string's tau_g2[1], so the prover's ck_main must be the SRS of the same string (hip.kzg_from_powers).  VIMZ_ERR_INVALID with a message: a NULL pointer,
  * n_pow < n or n_tau_g1 < 2n − 1, a coordinate not below q, a point not on its curve, tau_g1[0] or tau_g2[0] not the generator, beta_g2 or tau_g2[1] outside
- * the subgroup, e(tau_g1[1], G2) != e(G1, tau_g2[1]), e(beta_g1[0], G2) != e(G1, beta_g2), tau_g2[1] not matching the prover's SRS.  NOT judged: the
+ * the subgroup, e(tau_g1[1], G2) != e(G1, tau_g2[1]), e(beta_g1[0], G2) != e(G1, beta_g2), tau_g2[1] not matching the prover's SRS.  The
  * same-ratio property of the whole string (that every point is the next power of ONE tau, alpha·, beta· included) and subgroup membership of the other points of
- * tau_g2 — the caller vouches for the string, as for vimz_powers_lagrange.  The resulting object is an ordinary decider (prove, verify, vk, key_save).
+ * tau_g2 are judged by vimz_powers_verify, which is opt-in (hip.Decider(verify_powers=True) runs it first): this call does not.  The resulting object is an ordinary decider (prove, verify, vk, key_save).
  * seconds (optional) = {circuit synthesis, checks + upload, transforms, column sums, l/h scaling + key tables, total}. */
 int vimz_decider_setup_from_powers(vimz_cf* prover, int light, const uint64_t* tau_g1, size_t n_tau_g1, const uint64_t* tau_g2, const uint64_t* alpha_g1,
                                    const uint64_t* beta_g1, size_t n_pow, const uint64_t beta_g2[16], int form, vimz_decider** out, double seconds[6]);
+/* the domain n (vimz_decider_info's info[3]) a set-up of this prover's decider would work over, by synthesising the circuit alone (host; no key is made): what a
+ * caller needs to judge the prefix of a string (vimz_powers_verify: n_pow = n, n_tau_g1 = 2n − 1) BEFORE vimz_decider_setup_from_powers reads it */
+int vimz_decider_domain(vimz_cf* prover, int light, uint64_t* domain);
 void vimz_decider_free(vimz_decider* d);
 /* info = {constraints, wires, public inputs (36 + 2 len_z), domain size, non-zeros of A, B, C, rows of the CycleFold checks (0: light decider)} */
 int vimz_decider_info(const vimz_decider* d, uint64_t info[8]);

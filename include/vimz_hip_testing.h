@@ -99,6 +99,13 @@ int vimz_test_g16_column_sums(vimz_ctx* ctx, int group, const uint32_t* row_ptr,
 /* The h query of the same set-up (g16_h_query: k_point_diff, then k_scale_points in place): out_j = delta_inv·(P_(j+n) − P_j) for j < n − 1 over 2n − 1 points of
  * G1, n >= 2, and one canonical scalar below r.  Canonical on both sides, 8 words a point, the identity as zeros. */
 int vimz_test_g16_h_query(vimz_ctx* ctx, const uint64_t* tau_g1_xy, size_t n, const uint64_t delta_inv[4], uint64_t* out_xy);
+/* The two device stages of vimz_powers_verify (vimz_amd/csrc/g16_powers_verify.hip) on a caller's points, through the function the product runs on each array of a
+ * string.  group = 1: points of G1, 8 words each; 2: of G2, 16 words (x.c0, x.c1, y.c0, y.c1); form = VIMZ_FORM_*; the identity as zeros.
+ * _flags: flags[i] = 0 or the VIMZ_POWERS_COORD / _OFF_CURVE / _IDENTITY / _SUBGROUP finding of point i (k_powers_flags; the coordinates' range on the host), n >= 1.
+ * _rlc: out = S = sum rho_i·P_i, then S' = sum rho_i·P_(i+1), over i < n − 1 (k_powers_rlc twice, each reduced by g16_column_sums), n >= 2 points none of which
+ * is flagged, rho: 2 words of 64 bits a pair (any 128-bit value), out: 2 points in the form of the input. */
+int vimz_test_powers_flags(vimz_ctx* ctx, int group, const uint64_t* points, size_t n, int form, uint32_t* flags);
+int vimz_test_powers_rlc(vimz_ctx* ctx, int group, const uint64_t* points, size_t n, const uint64_t* rho, int form, uint64_t* out);
 /* The two set-ups a test compares byte for byte (vimz_decider_key_save): the trapdoor set-up (decider_setup_impl) with a GIVEN trapdoor — tau, alpha, beta, gamma,
  * delta: 4 canonical words each, non-zero, below r — and vimz_decider_setup_from_powers with a given delta.  Whoever knows these scalars can forge. */
 int vimz_testing_decider_setup_trapdoor(vimz_cf* prover, const uint64_t kzg_vk_g2[16], int light, const uint64_t td[20] /* tau, alpha, beta, gamma, delta */,

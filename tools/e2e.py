@@ -2,13 +2,14 @@
 """End-to-end run of one transformation on the GPU, the way `vimz -b nova-snark -f <t>` sequences it
 (vimz/src/nova_snark_backend/mod.rs:22-80): prepare input -> prepare folding (circuit + key) -> fold every row -> verify.
 Prints the span times the reference logs ("Prepare input", "Prepare folding", "Fold input", "Verify folded proof").
-usage: e2e.py <transformation> <resolution> [segments] [ivc|accumulator|cyclefold] [proof file prefix or -] [witness batch] [--ptau FILE]
+usage: e2e.py <transformation> <resolution> [segments] [ivc|accumulator|cyclefold] [proof file prefix or -] [witness batch] [--ptau FILE [--verify-ptau]]
 ivc (default): ONE proof object — the rows are proven as `segments` Nova IVCs of contiguous row segments folded concurrently and
 merged (vimz_ivc_merge), then compressed;
 accumulator: NIFS accumulators of the segments merged by a final fold;
 cyclefold: the Sonobe backend's sequence (vimz/src/sonobe_backend/mod.rs:52-95: prepare folding, fold input, verify folded proof) with Nova +
 CycleFold; with one segment also the decider (Prepare decider, Generate decider proof: vimz_decider_*; the full one, or VIMZ_E2E_DECIDER=light) and the calldata bytes.
---ptau FILE (cyclefold only): the KZG SRS and the decider's key come from that powers-of-tau string (iden3.read_ptau, hip.kzg_from_powers, hip.Decider(powers=))
+--ptau FILE (cyclefold only): the KZG SRS and the decider's key come from that powers-of-tau string (iden3.read_ptau, hip.kzg_from_powers, hip.Decider(powers=));
+--verify-ptau: the string is judged first (hip.verify_powers) and a refused one ends the run
 instead of a tau and a trapdoor drawn in this process."""
 import json
 import sys
@@ -24,12 +25,17 @@ from vimz_amd.distributed import fold_local_segments, fold_segments_merged  # no
 
 def main():
     powers = None
+    verify_ptau = "--verify-ptau" in sys.argv
+    if verify_ptau:
+        sys.argv.remove("--verify-ptau")
     if "--ptau" in sys.argv:
         k = sys.argv.index("--ptau")
         from vimz_amd import iden3
         with open(sys.argv[k + 1], "rb") as fp:
             powers = iden3.read_ptau(fp.read())
         del sys.argv[k:k + 2]
+    if verify_ptau and powers is None:
+        sys.exit("e2e.py: --verify-ptau goes with --ptau FILE")
     t, res = sys.argv[1], sys.argv[2]
     S = int(sys.argv[3]) if len(sys.argv) > 3 else 3      # (a lone, cold image: three segments — a fourth pays for itself only over repeated proofs, profiles/r06_segments_sweep.txt)
     mode = sys.argv[4] if len(sys.argv) > 4 else "ivc"
@@ -53,7 +59,7 @@ def main():
     pmode = mode if mode in ("ivc", "cyclefold") else "accumulator"
     if powers is not None and mode != "cyclefold":
         sys.exit("e2e.py: --ptau goes with the cyclefold mode")
-    ctxs, circuit, params, made, setup_split = folding.prepare_folding_overlapped(0, S, t, res, mode=pmode, batch=batch, powers=powers)
+    ctxs, circuit, params, made, setup_split = folding.prepare_folding_overlapped(0, S, t, res, mode=pmode, batch=batch, powers=powers, verify_powers=verify_ptau)
     batch = batch or folding.default_batch(circuit)
     th_in.join()
     rows, z0 = inp["rows"], inp["z0"]

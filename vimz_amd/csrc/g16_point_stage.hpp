@@ -111,4 +111,55 @@ VZ_HD void pt_diff(size_t j, size_t n, const Affine<F>* points, Affine<F>* out) 
   out[j] = to_affine(acc);
 }
 
+// ---- judging a powers-of-tau string (g16_powers_verify.hip: k_powers_flags, k_powers_rlc): what ONE thread does, looped on the CPU by tests/native/pt_verify_check.cpp ----
+
+// what a point of a string can be flagged with — the values of VIMZ_POWERS_* (include/vimz_hip.h); a coordinate not below q is the host's finding (bit 1)
+constexpr uint32_t PV_OFF_CURVE = 2, PV_IDENTITY = 4, PV_SUBGROUP = 8;
+constexpr unsigned RLC_CHUNK = 8;      // consecutive pairs of one thread of k_powers_rlc: they share the 128 doublings.  A wave runs an addition for every (bit, pair) some
+                                       // lane has set — nearly all —, so a point costs 128 addition slots + 128 / RLC_CHUNK doublings: 144 at 8 against 132 at 32, and a thread's
+                                       // serial chain is 128·(1 + RLC_CHUNK) operations.  At 32 a string of 2^18 left three quarters of the SIMDs empty and the chain set the time
+                                       // (profiles/powers_verify.txt); at 8 its 2^19 / 8 chunks are one wave a SIMD.
+constexpr int RLC_BITS = 128;          // bits of a rho
+
+// flags[index] = what is wrong with points[index], 0: nothing.  b: the curve's constant in the coordinates' form (y² = x³ + b).  order: the 8 canonical words of r
+// for a curve with a cofactor (the twist), and the point must then be killed by r — for a point of the subgroup the last addition is (r − 1)Q + Q, add_mixed's
+// cancellation: that branch is the accept path; NULL for G1 (cofactor one: on the curve is in the group).  An identity is flagged (a power of a non-zero tau never
+// is one) and not looked at further, nor is a point off its curve: r times it would be arithmetic on another curve.  Only the flag is written.
+template <class F>
+VZ_HD void pt_flags(size_t index, const Affine<F>* points, const F& b, const uint32_t* order, uint32_t* flags) {
+  const Affine<F> p = points[index];
+  uint32_t f = 0;
+  if (aff_is_identity(p)) f = PV_IDENTITY;
+  else if (!F::sqr(p.y).eq(F::add(F::mul(F::sqr(p.x), p.x), b))) f = PV_OFF_CURVE;
+  else if (order && !pt_scalar_mul(p, order).is_identity()) f = PV_SUBGROUP;
+  flags[index] = f;
+}
+
+// chunk `index` of a random linear combination over pairs of neighbours: out[index] = Σ rho_i · points[i + shift] over the pairs i of the chunk,
+// RLC_CHUNK·index <= i < min(RLC_CHUNK·(index + 1), n_pairs); rho_i = the 4 words rho[4i ..].  shift = 0 gives the chunks of S = Σ rho_i·P_i, shift = 1 those of
+// S' = Σ rho_i·P_(i+1): a string of ONE tau has S' = tau·S whatever the rho.  The 128 bit positions are walked once from the top: double, then add every point of the
+// chunk whose rho has the bit — one doubling serves the whole chunk.  A zero rho adds nothing, a partial last chunk is shorter; add_mixed handles the identity,
+// equal and opposite points.  Reads points[.. n_pairs − 1 + shift] and writes its own slot alone.
+template <class F>
+VZ_HD void pt_rlc_chunk(size_t index, const Affine<F>* points, size_t n_pairs, const uint32_t* rho, unsigned shift, Affine<F>* out) {
+  const size_t lo = (size_t)RLC_CHUNK * index, hi = lo + RLC_CHUNK < n_pairs ? lo + RLC_CHUNK : n_pairs;
+  XYZZ<F> acc = XYZZ<F>::identity();
+#pragma unroll 1
+  for (int b = RLC_BITS - 1; b >= 0; b--) {
+    acc = dbl(acc);
+#pragma unroll 1
+    for (size_t i = lo; i < hi; i++)
+      if ((rho[4 * i + (b >> 5)] >> (b & 31)) & 1u) add_mixed(acc, points[i + shift]);
+  }
+  out[index] = to_affine(acc);
+}
+
+// the plan (g16_colsum_plan.hpp) that sums the n_chunks chunk sums into ONE point: a single column that takes every chunk with coefficient one, through colsum_run
+inline bool rlc_sum_plan(size_t n_chunks, ColsumPlan* plan) {
+  if (!n_chunks || n_chunks >= ((size_t)1 << 31)) return false;
+  std::vector<ColsumUnit> units(n_chunks);
+  for (size_t t = 0; t < n_chunks; t++) units[t] = {(uint32_t)t, 0u};
+  return colsum_plan(nullptr, 0, units.data(), units.size(), nullptr, 0, BnFr::MOD.w, 1u, (uint32_t)n_chunks, plan, nullptr);
+}
+
 }  // namespace vz

@@ -53,3 +53,21 @@ hipError_t g16_column_sums(hipStream_t s, const ColsumDevice& dev, const G2PowAf
 // Queues on `s`: out[j] = dinv·(tau_g1[j + n] − tau_g1[j]) for j < n − 1 — the h query [(tau^n − 1)·tau^j / delta]G1 from the string's 2n − 1 powers: k_point_diff,
 // then k_scale_points in place.  dinv_canon: 8 canonical words on the device, wiped by the caller.  out: n − 1 points, not overlapping tau_g1.
 hipError_t g16_h_query(hipStream_t s, const G1Aff* tau_g1, size_t n, const uint32_t* dinv_canon, G1Aff* out);
+
+// ---- judging a string before a set-up trusts it (g16_powers_verify.hip: vimz_powers_verify) ------------------------------------------------------------------
+// the generators in Montgomery coordinates, and the OS's randomness (groth16.hip: what a proof's blinders are drawn from)
+G1Aff g16_g1_generator();
+G2PowAff g16_g2_generator();
+bool g16_os_random(void* buf, size_t n);
+// Queues on `s`: flags[i] = 0, or what is wrong with points[i] (g16_point_stage.hpp: pt_flags — the identity, off its curve, and for G2 not killed by r), one
+// thread per point, each writing its own 4 bytes.  order_canon: the 8 canonical words of r on the device (read for G2 alone).
+hipError_t g16_powers_flags(hipStream_t s, const G1Aff* points, size_t n, const uint32_t* order_canon, uint32_t* flags);
+hipError_t g16_powers_flags(hipStream_t s, const G2PowAff* points, size_t n, const uint32_t* order_canon, uint32_t* flags);
+// the chunk sums a combination over n_pairs pairs leaves for the reduction
+inline size_t g16_powers_rlc_chunks(size_t n_pairs) { return (n_pairs + vz::RLC_CHUNK - 1) / vz::RLC_CHUNK; }
+// Queues on `s`: out[0] = S = Σ rho_i·points[i], out[1] = S' = Σ rho_i·points[i + 1] over i < n_pairs (so n_pairs + 1 points are read), rho_i the 128 bits at
+// rho[4i ..] on the device: two launches of k_powers_rlc (shift 0 and 1; thread t sums the chunk t into chunks[t], g16_point_stage.hpp: pt_rlc_chunk), each followed
+// by g16_column_sums over `sum`, the plan of ONE column that takes every chunk with coefficient one (g16_point_stage.hpp: rlc_sum_plan, uploaded for this point size).
+// chunks: g16_powers_rlc_chunks(n_pairs) points.  out: affine as g16_column_sums leaves it (reduced Montgomery coordinates), the identity as zeros.
+hipError_t g16_powers_rlc(hipStream_t s, const G1Aff* points, size_t n_pairs, const uint32_t* rho, const ColsumDevice& sum, G1Aff* chunks, G1Aff* out);
+hipError_t g16_powers_rlc(hipStream_t s, const G2PowAff* points, size_t n_pairs, const uint32_t* rho, const ColsumDevice& sum, G2PowAff* chunks, G2PowAff* out);

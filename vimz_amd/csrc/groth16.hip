@@ -883,6 +883,11 @@ VerifierKey key_of(const vimz_decider* d) {
 
 }  // namespace
 
+// what judging a string (g16_powers_verify.hip) shares with the set-up: the generators and the OS's randomness the blinders are drawn from
+G1Aff g16_g1_generator() { return g1_generator(); }
+G2PowAff g16_g2_generator() { return g2_generator(); }
+bool g16_os_random(void* buf, size_t n) { return os_random(buf, n); }
+
 extern "C" {
 
 void vimz_decider_free(vimz_decider* d) {
@@ -926,6 +931,16 @@ int vimz_decider_setup_from_powers(vimz_cf* v, int light, const uint64_t* tau_g1
   if (!out || !tau_g1 || !tau_g2 || !alpha_g1 || !beta_g1 || !beta_g2) return vz_fail(v->ctx, VIMZ_ERR_INVALID, "vimz_decider_setup_from_powers: NULL argument");
   if (form != VIMZ_FORM_CANONICAL && form != VIMZ_FORM_MONTGOMERY) return vz_fail(v->ctx, VIMZ_ERR_INVALID, "vimz_decider_setup_from_powers: form is VIMZ_FORM_*");
   return decider_setup_powers_impl(v, light != 0, PowersString{tau_g1, n_tau_g1, tau_g2, alpha_g1, beta_g1, n_pow, beta_g2, form}, nullptr, out, seconds);
+}
+// The domain a set-up of this prover's decider works over, without a set-up: the circuit is synthesised (host only) and dropped.  For a caller that judges the
+// prefix of a string a set-up will read (vimz_powers_verify) before the set-up runs.
+int vimz_decider_domain(vimz_cf* v, int light, uint64_t* domain) {
+  if (!v) return VIMZ_ERR_INVALID;
+  if (!domain) return vz_fail(v->ctx, VIMZ_ERR_INVALID, "vimz_decider_domain: NULL argument");
+  std::unique_ptr<vimz_decider> d(new vimz_decider());
+  { const int rch = decider_setup_head(v, nullptr, light != 0, *d); if (rch) return rch; }
+  *domain = d->key.n;
+  return VIMZ_OK;
 }
 #ifdef VIMZ_TESTING
 // Host only, no GPU: the decider circuit (aug/decider.hpp) over the Nova + CycleFold recursion of the trivial step circuit with made-up commitments — the

@@ -79,15 +79,16 @@ class FoldingParams:
     """The analogue of nova-snark's PublicParams: R1CS shape + both commitment keys (BN254 G1 for the primary circuit, Grumpkin for
     the secondary), resident on one GPU."""
 
-    def __init__(self, ctx, circuit, ck, keygen_seconds, ck_secondary=None, kzg_vk=None, powers=None):
+    def __init__(self, ctx, circuit, ck, keygen_seconds, ck_secondary=None, kzg_vk=None, powers=None, verify_powers=False):
         self.ctx, self.circuit, self.ck, self.keygen_seconds, self.ck_secondary = ctx, circuit, ck, keygen_seconds, ck_secondary
         self.kzg_vk = kzg_vk      # backend "sonobe": [tau]G2 of the KZG SRS `ck` is (the decider's verifier needs it)
+        self.verify_powers = bool(verify_powers)      # the decider judges the prefix of the string it reads (hip.verify_powers) before its set-up
         self.powers = powers      # ... or the powers-of-tau string `ck` was taken from: hip.Decider(prover, powers=params.powers) derives its key from the same
 
     def decider(self, prover, light=False):
         """The decider over `prover` (a CycleFoldIVC made with these keys): from the string when the keys came from one, else by a trapdoor drawn here."""
         from . import hip
-        return hip.Decider(prover, powers=self.powers, light=light) if self.powers is not None else hip.Decider(prover, kzg_vk=self.kzg_vk, light=light)
+        return hip.Decider(prover, powers=self.powers, light=light, verify_powers=self.verify_powers) if self.powers is not None else hip.Decider(prover, kzg_vk=self.kzg_vk, light=light)
 
     def secondary_key(self):
         if self.ck_secondary is None:
@@ -106,7 +107,7 @@ def _refuse_powers_without_kzg(powers, sonobe):
         raise _lib.VimzError(_lib.ERR_INVALID, "prepare_folding: powers= is for the Sonobe backend (a KZG SRS); the nova-snark backend's key has no tau")
 
 
-def prepare_folding(ctx, transformation, resolution="HD", ck_label=b"ck", window_tables=15, backend="nova-snark", powers=None):
+def prepare_folding(ctx, transformation, resolution="HD", ck_label=b"ck", window_tables=15, backend="nova-snark", powers=None, verify_powers=False):
     """prepare_folding (folding.rs:20-25): build the step circuit and derive the commitment key on the GPU.
     window_tables: 13..16 = window tables T_j[i] = 2^(c j)·P_i of the key in HBM with ONE bucket set shared by all windows
     (vimz_bases_precompute; default 15: 17 x the key = 0.7 GB at HD, 17 digits per scalar instead of 24 — the large MSM of a step
@@ -117,7 +118,8 @@ def prepare_folding(ctx, transformation, resolution="HD", ck_label=b"ck", window
     `prepare_folding`, vimz/src/sonobe_backend/folding.rs:36-48): powers of a tau drawn from the OS's randomness and forgotten
     (vimz_kzg_setup), whose [tau]G2 is kept in FoldingParams.kzg_vk for the decider's verifier.
     powers (backend "sonobe" only): iden3.read_ptau's dictionary — the SRS is then the string's first n points (hip.kzg_from_powers: no tau is drawn), and
-    FoldingParams.decider derives the decider's key from the same string (hip.Decider(powers=))."""
+    FoldingParams.decider derives the decider's key from the same string (hip.Decider(powers=)).  verify_powers=True: the string's prefix each of the two reads is
+    judged first (hip.verify_powers); a refused string raises VimzError(ERR_INVALID).  Off by default."""
     _refuse_powers_without_kzg(powers, backend == "sonobe")
     t0 = time.time()
     circuit = Circuit(transformation, *default_shape(transformation, resolution))
@@ -126,15 +128,15 @@ def prepare_folding(ctx, transformation, resolution="HD", ck_label=b"ck", window
     kzg_vk = None
     if backend == "sonobe":
         from . import hip
-        ck, kzg_vk = hip.kzg_setup(ctx, n) if powers is None else hip.kzg_from_powers(ctx, powers, n)
+        ck, kzg_vk = hip.kzg_setup(ctx, n) if powers is None else hip.kzg_from_powers(ctx, powers, n, verify_powers=verify_powers)
     else:
         ck = ctx.bases_generate(_lib.CURVE_BN254_G1, n, ck_label)
     if window_tables:
         ck.precompute(16 if window_tables is True else int(window_tables))
-    return circuit, FoldingParams(ctx, circuit, ck, time.time() - t0, kzg_vk=kzg_vk, powers=powers)
+    return circuit, FoldingParams(ctx, circuit, ck, time.time() - t0, kzg_vk=kzg_vk, powers=powers, verify_powers=verify_powers and powers is not None)
 
 
-def prepare_folding_overlapped(device, segments, transformation, resolution="HD", window_tables=15, backend="nova-snark", mode="ivc", batch=0, ctxs=None, powers=None):
+def prepare_folding_overlapped(device, segments, transformation, resolution="HD", window_tables=15, backend="nova-snark", mode="ivc", batch=0, ctxs=None, powers=None, verify_powers=False):
     """prepare_folding for a proof made as `segments` concurrent row segments, with its parts side by side instead of one after another
     (once the fold takes 0.6 s the set-up is the largest span of an HD run).  What depends on what:
         contexts (HIP runtime, streams)      — nothing; one thread each
@@ -144,7 +146,7 @@ def prepare_folding_overlapped(device, segments, transformation, resolution="HD"
                                                 segments' provers are made side by side (ctypes releases the GIL around every library call)
     Returns (ctxs, circuit, params, provers, seconds: {contexts_and_circuit, keys, provers, total}).  mode: "ivc" (hip.IVC), "cyclefold"
     (hip.CycleFoldIVC over a KZG SRS), "accumulator" (hip.Prover).  Sequential equivalent: prepare_folding + one prover per context.
-    powers: as prepare_folding's (the Sonobe path only)."""
+    powers, verify_powers: as prepare_folding's (the Sonobe path only)."""
     import threading
     from . import hip
     _refuse_powers_without_kzg(powers, backend == "sonobe" or mode == "cyclefold")      # (before any context or thread exists)
@@ -194,7 +196,7 @@ def prepare_folding_overlapped(device, segments, transformation, resolution="HD"
     n = 1 << (max(circuit.n_wires, circuit.n_constraints) + (CYCLEFOLD_ROOM if sonobe else AUGMENTED_ROOM) - 1).bit_length()
     kzg_vk = None
     if sonobe:
-        ck, kzg_vk = hip.kzg_setup(ctxs[0], n) if powers is None else hip.kzg_from_powers(ctxs[0], powers, n)
+        ck, kzg_vk = hip.kzg_setup(ctxs[0], n) if powers is None else hip.kzg_from_powers(ctxs[0], powers, n, verify_powers=verify_powers)
     else:
         ck = ctxs[0].bases_generate(_lib.CURVE_BN254_G1, n, b"ck")
     if window_tables:
@@ -203,7 +205,7 @@ def prepare_folding_overlapped(device, segments, transformation, resolution="HD"
         x.join()
     if err:
         raise err[0]
-    params = FoldingParams(ctxs[0], circuit, ck, time.time() - t_cc, kzg_vk=kzg_vk, powers=powers)
+    params = FoldingParams(ctxs[0], circuit, ck, time.time() - t_cc, kzg_vk=kzg_vk, powers=powers, verify_powers=verify_powers and powers is not None)
     ck2 = params.secondary_key() if mode in ("ivc", "cyclefold") else None      # (mode "none": keys only, the caller makes its provers)
     t_keys = time.time()
     batch = batch or default_batch(circuit)

@@ -871,12 +871,58 @@ def kzg_setup(ctx, n, seed=None):
 _BN254_Q = 21888242871839275222246405745257275088696311157297823662689037894645226208583
 
 
-def kzg_from_powers(ctx, powers, n):
+POWERS_PROBLEMS = {0x1: "a coordinate is not below q", 0x2: "a point is not on its curve", 0x4: "a point is the identity", 0x8: "a point of G2 is outside the subgroup",
+                   0x10: "a first point is not the generator", 0x20: "tau_g1 is not the powers of one tau", 0x40: "alpha_g1 is not the powers of one tau",
+                   0x80: "beta_g1 is not the powers of one tau", 0x100: "tau_g2 is not the powers of one tau", 0x200: "tau_g1[1] and tau_g2[1] are not of one tau",
+                   0x400: "beta_g1[0] and beta_g2 are not of one beta"}      # VIMZ_POWERS_*
+POWERS_ARRAYS = (None, "tau_g1", "tau_g2", "alpha_g1", "beta_g1", "beta_g2")      # first_bad[0]
+
+
+def verify_powers(ctx, powers, n=None, seconds=None, n_tau_g1=None):
+    """vimz_powers_verify: judges a powers-of-tau string (iden3.read_ptau's dictionary, the file's Montgomery form) on the GPU — what snarkjs's `powersoftau verify`
+    does: every point on its curve and not the identity, every point of G2 in the subgroup, each array the powers of ONE tau (random combinations of 128-bit
+    scalars and six pairing equations), the halves of one tau, beta_g1 and beta_g2 of one beta, the first points the generators.  n: the points of tau_g2, alpha_g1
+    and beta_g1 to judge, tau_g1 then 2n − 1 (or n_tau_g1) — the prefix a set-up over a domain of n reads; None: the whole string.  Returns (result, first_bad):
+    result 0 = accepted, otherwise a union of POWERS_PROBLEMS' bits; first_bad = (array number — POWERS_ARRAYS names it —, index) of the first per-point
+    finding, (0, 0) when there is none.  seconds: a list that receives [host conversion, per-point flags, combinations, pairings].  VimzError(ERR_INVALID): n
+    below 2 or beyond the string."""
+    a = {name: np.ascontiguousarray(powers[name], dtype=np.uint64).reshape(-1, 8 * group) for name, group in _LAGRANGE_ARRAYS + (("beta_g2", 2),)}
+    have = min(a["tau_g2"].shape[0], a["alpha_g1"].shape[0], a["beta_g1"].shape[0])
+    n_pow = have if n is None else int(n)
+    n_g1 = int(n_tau_g1) if n_tau_g1 is not None else a["tau_g1"].shape[0] if n is None else 2 * n_pow - 1
+    if n_pow < 2 or n_pow > have or n_g1 < n_pow or n_g1 > a["tau_g1"].shape[0] or a["beta_g2"].shape[0] < 1:
+        raise L.VimzError(L.ERR_INVALID, f"verify_powers: {n_pow} points (tau_g1: {n_g1}) of a string that holds {have} (tau_g1: {a['tau_g1'].shape[0]}); needs 2 <= n <= the string's length")
+    vp = C.c_void_p
+    result, first, sec = C.c_uint32(0), np.zeros(2, dtype=np.uint64), (C.c_double * 4)()
+    ctx.lib.vimz_powers_verify.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, C.c_size_t, vp, C.c_int, C.POINTER(C.c_uint32), vp, C.POINTER(C.c_double)]
+    ctx._chk(ctx.lib.vimz_powers_verify(ctx.h, _ptr(a["tau_g1"]), n_g1, _ptr(a["tau_g2"]), _ptr(a["alpha_g1"]), _ptr(a["beta_g1"]), n_pow, _ptr(a["beta_g2"]), L.FORM_MONTGOMERY,
+                                        C.byref(result), _ptr(first), sec))
+    if seconds is not None:
+        seconds[:] = list(sec)
+    return int(result.value), (int(first[0]), int(first[1]))
+
+
+def powers_problems(result):
+    """the names of a verdict's bits"""
+    return [name for bit, name in POWERS_PROBLEMS.items() if result & bit]
+
+
+def require_good_powers(ctx, powers, n, who, n_tau_g1=None):
+    """verify_powers over the prefix a set-up reads; VimzError(ERR_INVALID) naming the problems and first_bad unless the string is accepted"""
+    result, first = verify_powers(ctx, powers, n, n_tau_g1=n_tau_g1)
+    if result:
+        at = f" (first: {POWERS_ARRAYS[first[0]]}[{first[1]}])" if first[0] else ""
+        raise L.VimzError(L.ERR_INVALID, f"{who}: the powers-of-tau string is refused: " + "; ".join(powers_problems(result)) + at)
+
+
+def kzg_from_powers(ctx, powers, n, verify_powers=False):
     """KZG's keys from a powers-of-tau string (iden3.read_ptau's dictionary: rows of uint64 words in the file's Montgomery form) instead of kzg_setup: the srs is
     the string's first n points [tau^k]G1 as Bases, vk_g2 = [tau]G2 = tau_g2[1] as the canonical (4, 4) array Decider takes — no tau is drawn in this process, and
     a decider key derived from the same string shares its tau (as snarkjs's set-ups over one `.ptau` do).  VimzError(ERR_INVALID): n below 2 (the decider checks
     e(srs[1], G2) = e(G1, vk)), a string shorter than n, a first power that is not the generator, a coordinate of tau_g2[1] not below q.  The points are not
-    judged otherwise: that pairing check is the decider's, the same-ratio check of every power is nobody's yet."""
+    judged otherwise unless verify_powers is true: the string's first n points (tau_g1: 2n − 1, or as many as it holds) then go through vimz_powers_verify first
+    (hip.verify_powers: subgroup membership and the same-ratio check of every power) and a refused string raises VimzError(ERR_INVALID) naming the problems.
+    That check is opt-in; the pairing check of srs[1] against the key is the decider's."""
     g1 = np.ascontiguousarray(powers["tau_g1"], dtype=np.uint64).reshape(-1, 8)
     g2 = np.ascontiguousarray(powers["tau_g2"], dtype=np.uint64).reshape(-1, 16)
     n = int(n)
@@ -889,6 +935,9 @@ def kzg_from_powers(ctx, powers, n):
     vk = ints(g2[1])
     if max(vk) >= _BN254_Q:
         raise L.VimzError(L.ERR_INVALID, "kzg_from_powers: a coordinate of tau_g2[1] is not below the modulus")
+    if verify_powers:
+        have = min(np.asarray(powers[name]).reshape(-1, 8 * group).shape[0] for name, group in _LAGRANGE_ARRAYS[1:])      # (tau_g1 is about twice as long as the others)
+        require_good_powers(ctx, powers, min(n, have), "kzg_from_powers", n_tau_g1=min(2 * n - 1, g1.shape[0]))
     minv = pow(mont, -1, _BN254_Q)
     vk_words = np.frombuffer(b"".join((c * minv % _BN254_Q).to_bytes(32, "little") for c in vk), dtype="<u8").reshape(4, 4).astype(np.uint64)
     return ctx.bases_upload(L.CURVE_BN254_G1, g1[:n], form=L.FORM_MONTGOMERY), vk_words
@@ -916,7 +965,8 @@ def lagrange_from_powers(ctx, powers, logn):
     [L_j(tau)]G2 — what snarkjs's `powersoftau prepare phase2` derives, by four calls of vimz_powers_lagrange (the inverse transform over points, on the GPU).
     With them a commitment to a polynomial given by its evaluations e is ctx.msm over the tau_g1 rows and e.  VimzError(ERR_INVALID), before any GPU work: logn
     below 1 or above the string's power, an array shorter than n; from the library: a coordinate not below q, a point not on its curve.  Subgroup membership
-    in G2 and the same-ratio property of the string are not judged."""
+    in G2 and the same-ratio property of the string are judged by hip.verify_powers (vimz_powers_verify), which is opt-in: this call does not run it (DESIGN.md §8
+    item 5)."""
     logn = int(logn)
     if logn < 1 or logn > int(powers["power"]):
         raise L.VimzError(L.ERR_INVALID, f"lagrange_from_powers: logn = {logn} with a string of power {int(powers['power'])} (needs 1 <= logn <= the power)")
@@ -961,14 +1011,17 @@ class Decider:
     powers: iden3.read_ptau's dictionary instead — vimz_decider_setup_from_powers: the key is derived on the GPU from the string's points, so tau, alpha and beta
     are the string's and never in this process, gamma = 1, and only delta is drawn here (and forgotten).  kzg_vk is then the string's tau_g2[1] — passing one as
     well is refused — and the prover's ck_main must come from the same string (kzg_from_powers).  `delta` (an int; with powers only) selects the TEST set-up of
-    libvimz_hip_testing.so with that delta."""
+    libvimz_hip_testing.so with that delta.  verify_powers=True (with powers only): the prefix the set-up reads — the circuit's domain n of tau_g2, alpha_g1, beta_g1
+    and 2n − 1 of tau_g1 — goes through hip.verify_powers first, and a refused string raises VimzError(ERR_INVALID) naming the problems before any key is made."""
     RESULT_BITS = {1: "fewer than two steps", 2: "KZG opening of cmW", 4: "KZG opening of cmE", 8: "Groth16", 16: "a word pair is not a curve point"}
 
-    def __init__(self, prover, kzg_vk=None, seed=None, light=False, powers=None, delta=None):
+    def __init__(self, prover, kzg_vk=None, seed=None, light=False, powers=None, delta=None, verify_powers=False):
         if powers is not None and (kzg_vk is not None or seed is not None):
             raise L.VimzError(L.ERR_INVALID, "Decider: powers= brings its own KZG verifying key (the string's tau_g2[1]) and draws no trapdoor: pass neither kzg_vk= nor seed= with it")
         if delta is not None and powers is None:
             raise L.VimzError(L.ERR_INVALID, "Decider: delta= goes with powers= only")
+        if verify_powers and powers is None:
+            raise L.VimzError(L.ERR_INVALID, "Decider: verify_powers= goes with powers= only")
         self.prover, self.ctx = prover, prover.ctx
         self.light = bool(light)
         lib = self.ctx.lib
@@ -982,6 +1035,11 @@ class Decider:
         lib.vimz_decider_prove.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_double)]
         lib.vimz_decider_verify.argtypes = [vp, C.c_uint64, vp, vp, vp, C.POINTER(C.c_uint32)]
         if powers is not None:
+            if verify_powers:
+                lib.vimz_decider_domain.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64)]
+                domain = C.c_uint64(0)
+                self.ctx._chk(lib.vimz_decider_domain(prover.h, int(self.light), C.byref(domain)))
+                require_good_powers(self.ctx, powers, int(domain.value), "Decider")
             self._setup_from_powers(powers, delta)
             return
         h = vp()

@@ -132,10 +132,11 @@ def split_witness(r1cs, wtns_values):
 
 
 def _decider_key(argv):
-    """decider-key FILE.ptau TRANSFORMATION RESOLUTION OUT.key [--light]: the decider's Groth16 key pair for that step circuit, derived from the string on GPU 0
-    (hip.Decider(powers=): tau, alpha, beta are the string's, delta is drawn here and forgotten), as vimz_decider_key_save's bytes."""
-    light = "--light" in argv
-    args = [a for a in argv if a != "--light"]
+    """decider-key FILE.ptau TRANSFORMATION RESOLUTION OUT.key [--light] [--verify]: the decider's Groth16 key pair for that step circuit, derived from the string on GPU 0
+    (hip.Decider(powers=): tau, alpha, beta are the string's, delta is drawn here and forgotten), as vimz_decider_key_save's bytes.  --verify: the prefixes of the
+    string the SRS and the set-up read are judged first (hip.verify_powers); a refused string ends the command with VimzError."""
+    light, verify = "--light" in argv, "--verify" in argv
+    args = [a for a in argv if a not in ("--light", "--verify")]
     if len(args) != 5 or any(a.startswith("--") for a in args):
         print(USAGE, file=sys.stderr)
         return 2
@@ -144,7 +145,7 @@ def _decider_key(argv):
         powers = read_ptau(fp.read())
     ctx = hip.Context(0)
     try:
-        circuit, params = folding.prepare_folding(ctx, args[2], args[3], window_tables=0, backend="sonobe", powers=powers)
+        circuit, params = folding.prepare_folding(ctx, args[2], args[3], window_tables=0, backend="sonobe", powers=powers, verify_powers=verify)
         cf = hip.CycleFoldIVC(ctx, circuit, params.ck, params.secondary_key(), max_batch=1)
         try:
             dec = params.decider(cf, light=light)
@@ -162,16 +163,45 @@ def _decider_key(argv):
     return 0
 
 
+def _verify(argv):
+    """verify FILE.ptau [POINTS]: judges the string on GPU 0 (hip.verify_powers: POINTS of tau_g2, alpha_g1, beta_g1 and 2·POINTS − 1 of tau_g1; without POINTS the
+    whole string), prints the verdict and the times; exit status 0 accepted, 1 refused."""
+    if len(argv) not in (2, 3):
+        print(USAGE, file=sys.stderr)
+        return 2
+    from . import hip
+    with open(argv[1], "rb") as fp:
+        powers = read_ptau(fp.read())
+    n = int(argv[2]) if len(argv) == 3 else None
+    sec = [0.0] * 4
+    ctx = hip.Context(0)
+    try:
+        result, first = hip.verify_powers(ctx, powers, n, seconds=sec)
+    finally:
+        ctx.close()
+    what = "the whole string" if n is None else f"{n} points (tau_g1: {2 * n - 1})"
+    times = f"host conversion {sec[0]:.3f} s, per-point flags {sec[1]:.3f} s, combinations {sec[2]:.3f} s, pairings {sec[3]:.3f} s"
+    if not result:
+        print(f"verify: {argv[1]} (power {int(powers['power'])}), {what}: accepted ({times})")
+        return 0
+    at = f"; first: {hip.POWERS_ARRAYS[first[0]]}[{first[1]}]" if first[0] else ""
+    print(f"verify: {argv[1]} (power {int(powers['power'])}), {what}: REFUSED (0x{result:x}): " + "; ".join(hip.powers_problems(result)) + f"{at} ({times})")
+    return 1
+
+
 USAGE = ("usage: python -m vimz_amd.iden3 lagrange FILE.ptau LOGN OUT.npz\n"
-         "       python -m vimz_amd.iden3 decider-key FILE.ptau TRANSFORMATION RESOLUTION OUT.key [--light]")
+         "       python -m vimz_amd.iden3 decider-key FILE.ptau TRANSFORMATION RESOLUTION OUT.key [--light] [--verify]\n"
+         "       python -m vimz_amd.iden3 verify FILE.ptau [POINTS]")
 
 
 def _main(argv):
     """python -m vimz_amd.iden3 lagrange FILE.ptau LOGN OUT.npz: the string's Lagrange bases over the domain of 2^LOGN points (hip.lagrange_from_powers, on GPU 0)
     as an .npz of tau_g1, alpha_g1, beta_g1 (n, 8) and tau_g2 (n, 16) in the file's Montgomery form, with logn.
-    python -m vimz_amd.iden3 decider-key ...: _decider_key."""
+    python -m vimz_amd.iden3 decider-key ...: _decider_key.  python -m vimz_amd.iden3 verify ...: _verify."""
     if argv and argv[0] == "decider-key":
         return _decider_key(argv)
+    if argv and argv[0] == "verify":
+        return _verify(argv)
     if len(argv) != 4 or argv[0] != "lagrange":
         print(USAGE, file=sys.stderr)
         return 2
