@@ -577,10 +577,51 @@ int vimz_decider_info(const vimz_decider* d, uint64_t info[8]);
 int64_t vimz_decider_vk(const vimz_decider* d, void* buf, size_t cap);
 /* The key pair at rest (bytes; layout: vimz_amd/csrc/groth16.hip): a set-up made once per circuit, or a key made elsewhere in this layout (the library then never
  * sees its trapdoor).  vimz_decider_setup_from_powers makes such a key from a ceremony's powers of tau with one local delta; further
- * delta contributions to a saved key are a follow-up.  _save returns the byte size (copies when cap suffices); _load checks sizes, the public-parameter hash and the
+ * delta contributions to a saved key: vimz_decider_key_contribute below.  _save returns the byte size (copies when cap suffices); _load checks sizes, the public-parameter hash and the
  * verifying part's points, and takes the queries as they are (a loaded key is trusted like any common reference string). */
 int64_t vimz_decider_key_save(vimz_decider* d, void* buf, size_t cap);
 int vimz_decider_key_load(vimz_cf* prover, const void* buf, size_t len, vimz_decider** out);
+/* A further delta contribution to a saved key (phase 2 of a Groth16 ceremony; what snarkjs calls `zkey contribute`), on key BYTES: the layout is read from the blob's
+ * own header, so a contributor needs a context and no prover.  delta' != 0 and a nonce come from the OS and are wiped on every path, host and device; delta1 and delta2
+ * become delta'·delta1 and delta'·delta2 (host); the l and h queries, side by side in the blob, are multiplied by 1/delta' on the GPU as one array; every other byte is
+ * copied.  key_out may be key_in.  Returns the byte size (= len; nothing is written, and no delta' drawn, when key_out is NULL or cap is short), or VIMZ_ERR_INVALID with a
+ * message: a blob with the wrong magic or length, a coordinate (of delta1, delta2, l or h) not below q, a delta point off its curve or the identity, delta2 outside
+ * the subgroup.  record_out: VIMZ_KEYCHAIN_RECORD_WORDS little-endian words — this project's own format (vimz_amd/csrc/g16_key_contrib.hpp), NOT a section of snarkjs's
+ * `.zkey`: magic "VG16CTR1", delta1 after (8), delta2 after (16), T (8), z (4), a Schnorr proof of knowledge of delta' over the base delta1_before bound to the key's
+ * header and pp_hash.  Records are kept apart from the key, one after another: the key format is unchanged.  seconds (optional) = {host, device (upload, scaling,
+ * download), total}. */
+#define VIMZ_KEYCHAIN_RECORD_WORDS 37
+int64_t vimz_decider_key_contribute(vimz_ctx* ctx, const void* key_in, size_t len, void* key_out, size_t cap, uint64_t record_out[37], double seconds[3]);
+/* Judges a chain of contributions (`zkey verify`): `final_key` is `origin` after the n_records contributions of `records` (37 words each, in order; n_records may be 0).
+ * Returns VIMZ_OK whenever the chain was judged: a bad chain is a verdict, not an error.  *result = 0: accepted; otherwise VIMZ_KEYCHAIN_* bits.  Stage by stage, a stage
+ * only when the ones before it found nothing:  the POINTS — every delta1_j, delta2_j, T_j and every point of l‖h of both keys has coordinates below q and is on its curve,
+ * delta points are not the identity, every delta2_j is killed by r, a point of l‖h is the identity only where the other key's is too (per-point work on l‖h: the GPU);
+ * the FIXED PART — the keys are the same words outside delta1, delta2, l and h;  the EQUATIONS, all evaluated — e(delta1_j, G2) = e(G1, delta2_j) and
+ * z_j·delta1_(j−1) = T_j + c_j·delta1_j for every record, the last record's delta points (the origin's, without records) are the final key's, and the same-ratio
+ * check of the end points: S = sum rho_i·P_i over the origin's l‖h, S' = sum rho_i·P'_i over the final's (one GPU pass under rho_i of 128 bits from the OS, wiped),
+ * e(S', delta2_final) = e(S, delta2_origin) — wrongly accepted with probability at most 2^-128.
+ * first_bad = {VIMZ_KEYCHAIN_AT_*, index}: the first finding's place — for _ORIGIN_DELTA / _FINAL_DELTA the index is 0 (delta1) or 1 (delta2); for _RECORD the record's
+ * number; for _ORIGIN_LH / _FINAL_LH the point's index in l‖h; for _FIXED_PART the offset in 64-bit words of the first difference; {0, 0} when only _LAST or _RATIO fail.
+ * A verified chain means: the final key is sound if the origin key is and ANY ONE contributor forgot their delta'.  That the origin key derives from a given
+ * string and circuit is not judged here; there is no random beacon.  seconds (optional) = {host conversion and host point checks, per-point flags (upload included),
+ * combination, equations}.  VIMZ_ERR_INVALID: a NULL pointer (seconds apart), a key or a record with the wrong magic or length. */
+#define VIMZ_KEYCHAIN_COORD 0x1u          /* a coordinate is not below q */
+#define VIMZ_KEYCHAIN_OFF_CURVE 0x2u      /* a point is not on its curve */
+#define VIMZ_KEYCHAIN_IDENTITY 0x4u       /* a delta point is the identity, or a point of l‖h is in one key only */
+#define VIMZ_KEYCHAIN_SUBGROUP 0x8u       /* a delta2 is outside the subgroup of order r */
+#define VIMZ_KEYCHAIN_FIXED_PART 0x10u    /* the keys differ outside delta1, delta2, l and h */
+#define VIMZ_KEYCHAIN_DELTA_HALVES 0x20u  /* a record's delta1 and delta2 are not of one delta */
+#define VIMZ_KEYCHAIN_KNOWLEDGE 0x40u     /* a record's proof of knowledge fails over the delta1 before it */
+#define VIMZ_KEYCHAIN_LAST 0x80u          /* the last record's delta points are not the final key's */
+#define VIMZ_KEYCHAIN_RATIO 0x100u        /* l‖h of the final key is not l‖h of the origin over the ratio of their delta2 */
+#define VIMZ_KEYCHAIN_AT_ORIGIN_DELTA 1
+#define VIMZ_KEYCHAIN_AT_FINAL_DELTA 2
+#define VIMZ_KEYCHAIN_AT_RECORD 3
+#define VIMZ_KEYCHAIN_AT_ORIGIN_LH 4
+#define VIMZ_KEYCHAIN_AT_FINAL_LH 5
+#define VIMZ_KEYCHAIN_AT_FIXED_PART 6
+int vimz_decider_key_verify_contributions(vimz_ctx* ctx, const void* origin, size_t origin_len, const void* final_key, size_t final_len, const uint64_t* records, size_t n_records,
+                                          uint32_t* result, uint64_t first_bad[2], double seconds[4]);
 /* Decider::prove for the IVC proof `ivc` holds (same shapes and keys as the decider's prover; left unchanged; at least one step): final fold, KZG
  * openings, Groth16 proof.  words_out: the 25 calldata words (vimz_amd/calldata.py names them), public_out: the info[2] public inputs; canonical,
  * 4 little-endian limbs each.  VIMZ_ERR_UNSAT when the proof does not satisfy the decider's statement (full decider: including a running CycleFold

@@ -113,6 +113,18 @@ int vimz_testing_decider_setup_trapdoor(vimz_cf* prover, const uint64_t kzg_vk_g
 int vimz_testing_decider_setup_from_powers_delta(vimz_cf* prover, int light, const uint64_t* tau_g1, size_t n_tau_g1, const uint64_t* tau_g2, const uint64_t* alpha_g1,
                                                  const uint64_t* beta_g1, size_t n_pow, const uint64_t beta_g2[16], int form, const uint64_t delta[4], vimz_decider** out,
                                                  double seconds[6]);
+/* vimz_decider_key_contribute (vimz_amd/csrc/g16_key_contrib.hip) with a GIVEN delta' and nonce — 4 canonical words each, below r, delta' non-zero — so that a test
+ * compares the key and the record byte for byte.  Whoever knows delta' can undo the contribution. */
+int64_t vimz_testing_decider_key_contribute_delta(vimz_ctx* ctx, const void* key_in, size_t len, void* key_out, size_t cap, uint64_t record_out[37], const uint64_t delta[4],
+                                                  const uint64_t nonce[4], double seconds[3]);
+/* The device stage of vimz_decider_key_verify_contributions' same-ratio check on a caller's points, through the functions the product runs: out = S = sum rho_i·before_i,
+ * then S' = sum rho_i·after_i over i < n (k_ratio_rlc: one launch over both arrays, reduced by g16_column_sums over a plan of two columns).  n >= 1 points of G1 each,
+ * 8 words a point, form = VIMZ_FORM_*, the identity as zeros, every point on the curve; rho: 2 words of 64 bits a point (any 128-bit value); out: 2 points in the form
+ * of the input.  _forms: the same with launches = 1, or launches = 2 — the two sums through two launches of k_powers_rlc (shift 0 each), what the single launch is
+ * measured against (profiles/key_contrib.txt) —, the combination queued `reps` times on the uploaded arrays, rep_seconds[r] (optional) = launch to synchronise. */
+int vimz_test_ratio_rlc(vimz_ctx* ctx, const uint64_t* before, const uint64_t* after, size_t n, const uint64_t* rho, int form, uint64_t* out /* S, S' */);
+int vimz_test_ratio_rlc_forms(vimz_ctx* ctx, const uint64_t* before, const uint64_t* after, size_t n, const uint64_t* rho, int form, int launches, int reps, uint64_t* out,
+                              double* rep_seconds);
 /* The chains of the full decider's check 5 (vimz_amd/csrc/aug/decider_cf.hpp: every scalar walks the 127 two-bit windows of its generator's table by affine
  * additions from the derived generator H) over a caller's generators and scalars, through the functions the prover calls: where = 0 the host's
  * (cf_open_chains_host; ctx may be NULL), where = 1 the device's (k_cf_open_chains, the scalars uploaded in Montgomery form as the prover holds them, both

@@ -162,4 +162,22 @@ inline bool rlc_sum_plan(size_t n_chunks, ColsumPlan* plan) {
   return colsum_plan(nullptr, 0, units.data(), units.size(), nullptr, 0, BnFr::MOD.w, 1u, (uint32_t)n_chunks, plan, nullptr);
 }
 
+// ---- the same-ratio check of two keys' l‖h arrays (g16_key_contrib.hip: k_ratio_rlc): what ONE thread does, looped on the CPU by tests/native/key_contrib_check.cpp ----
+
+// chunk `index` of row `row` of ONE launch over two arrays of n points under ONE vector of rho: row 0 sums the chunk of `before`, row 1 that of `after`, as
+// pt_rlc_chunk sums it with shift 0 — out[row·n_chunks + index] = Σ rho_i·P_i over RLC_CHUNK·index <= i < min(RLC_CHUNK·(index + 1), n).  The two rows share
+// nothing but what they read: a thread writes its own slot alone.
+template <class F>
+VZ_HD void pt_ratio_chunk(size_t index, unsigned row, const Affine<F>* before, const Affine<F>* after, size_t n, size_t n_chunks, const uint32_t* rho, Affine<F>* out) {
+  pt_rlc_chunk(index, row ? after : before, n, rho, 0u, out + (size_t)row * n_chunks);
+}
+
+// the plan of TWO columns over the 2·n_chunks chunk sums k_ratio_rlc leaves: column 0 takes the first n_chunks (S), column 1 the rest (S')
+inline bool ratio_sum_plan(size_t n_chunks, ColsumPlan* plan) {
+  if (!n_chunks || n_chunks >= ((size_t)1 << 30)) return false;
+  std::vector<ColsumUnit> units(2 * n_chunks);
+  for (size_t t = 0; t < n_chunks; t++) { units[t] = {(uint32_t)t, 0u}; units[n_chunks + t] = {(uint32_t)(n_chunks + t), 1u}; }
+  return colsum_plan(nullptr, 0, units.data(), units.size(), nullptr, 0, BnFr::MOD.w, 2u, (uint32_t)(2 * n_chunks), plan, nullptr);
+}
+
 }  // namespace vz

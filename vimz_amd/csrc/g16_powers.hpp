@@ -71,3 +71,15 @@ inline size_t g16_powers_rlc_chunks(size_t n_pairs) { return (n_pairs + vz::RLC_
 // chunks: g16_powers_rlc_chunks(n_pairs) points.  out: affine as g16_column_sums leaves it (reduced Montgomery coordinates), the identity as zeros.
 hipError_t g16_powers_rlc(hipStream_t s, const G1Aff* points, size_t n_pairs, const uint32_t* rho, const ColsumDevice& sum, G1Aff* chunks, G1Aff* out);
 hipError_t g16_powers_rlc(hipStream_t s, const G2PowAff* points, size_t n_pairs, const uint32_t* rho, const ColsumDevice& sum, G2PowAff* chunks, G2PowAff* out);
+#ifdef VIMZ_TESTING
+// ONE pass of the above without its reduction — chunks[t] = the sum of chunk t with that shift (0 or 1) —: what the two-launch form of the same-ratio check of two
+// keys is measured with (g16_key_contrib.hip, profiles/key_contrib.txt); in the testing library alone
+hipError_t g16_powers_rlc_pass(hipStream_t s, const G1Aff* points, size_t n_pairs, const uint32_t* rho, unsigned shift, G1Aff* chunks);
+#endif
+
+// ---- further delta contributions to a saved key (g16_key_contrib.hip: vimz_decider_key_verify_contributions) ------------------------------------------------
+// Queues on `s`: out[0] = S = Σ rho_i·before[i], out[1] = S' = Σ rho_i·after[i] over i < n, rho_i the 128 bits at rho[4i ..] on the device: ONE launch of k_ratio_rlc over
+// a grid of (chunks, 2) — blockIdx.y = 0 sums `before`, 1 `after`; thread t of a row sums its chunk into chunks[row·n_chunks + t] (g16_point_stage.hpp:
+// pt_ratio_chunk) —, then g16_column_sums over `sum`, the plan of TWO columns of ratio_sum_plan uploaded for G1.  chunks: 2·g16_powers_rlc_chunks(n) points.  out: as
+// g16_column_sums leaves it (reduced Montgomery coordinates, the identity as zeros).
+hipError_t g16_ratio_rlc(hipStream_t s, const G1Aff* before, const G1Aff* after, size_t n, const uint32_t* rho, const ColsumDevice& sum, G1Aff* chunks, G1Aff* out);

@@ -72,6 +72,14 @@ hipError_t g16_powers_rlc(hipStream_t s, const G1Aff* points, size_t n_pairs, co
 hipError_t g16_powers_rlc(hipStream_t s, const G2PowAff* points, size_t n_pairs, const uint32_t* rho, const ColsumDevice& sum, G2PowAff* chunks, G2PowAff* out) {
   return powers_rlc<Fq2>(s, points, n_pairs, rho, sum, chunks, out);
 }
+#ifdef VIMZ_TESTING
+hipError_t g16_powers_rlc_pass(hipStream_t s, const G1Aff* points, size_t n_pairs, const uint32_t* rho, unsigned shift, G1Aff* chunks) {
+  if (!points || !rho || !chunks || !n_pairs || n_pairs >= ((size_t)1 << 31) || shift > 1) return hipErrorInvalidValue;
+  const size_t n_chunks = g16_powers_rlc_chunks(n_pairs);
+  hipLaunchKernelGGL(k_powers_rlc<Fq>, dim3(pv_blocks(n_chunks)), dim3(PT_BLOCK), 0, s, points, n_pairs, n_chunks, rho, shift, chunks);
+  return hipGetLastError();
+}
+#endif
 namespace {
 
 double pv_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }

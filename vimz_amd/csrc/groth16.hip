@@ -19,6 +19,7 @@
 #include "aug/decider.hpp"
 #include "decider_chains.hpp"
 #include "g16_powers.hpp"
+#include "g16_key_contrib.hpp"
 #include "pairing.hpp"
 #include "vecops_api.hpp"
 #ifdef VIMZ_TESTING
@@ -1268,7 +1269,7 @@ int64_t vimz_decider_vk(const vimz_decider* d, void* buf, size_t cap) {
 // alpha1, beta1, delta1 (8 each), beta2, gamma2, delta2 (16 each), IC (8 x (n_pub + 1)), then the queries a (8 m), b1 (8 m), l (8 (m - n_pub - 1)), h (8 (n - 1)), b2 (16 m).
 // A loaded key is TRUSTED like any common reference string: its points are range- and curve-checked for the verifying part, the queries are taken as they are
 // (a wrong query makes proofs that do not verify, nothing worse).
-static const uint64_t G16_KEY_MAGIC = 0x3259454b36314756ull;      // "VG16KEY2"
+static const uint64_t G16_KEY_MAGIC = vz::keyc::KEY_MAGIC;          // "VG16KEY2" (g16_key_contrib.hpp reads the layout below from a blob's own header)
 static const size_t G16_KEY_HEADER = 7;
 int64_t vimz_decider_key_save(vimz_decider* d, void* buf, size_t cap) {
   if (!d) return VIMZ_ERR_INVALID;

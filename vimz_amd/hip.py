@@ -986,6 +986,67 @@ def _seeded(ctx, name):
     return getattr(ctx.lib, name)
 
 
+KEYCHAIN_BITS = {0x1: "a coordinate is not below q", 0x2: "a point is not on its curve", 0x4: "a delta point is the identity, or a point of l‖h is in one key only",
+                 0x8: "a delta2 is outside the subgroup", 0x10: "the keys differ outside delta1, delta2, l and h", 0x20: "a record's delta1 and delta2 are not of one delta",
+                 0x40: "a record's proof of knowledge fails", 0x80: "the last record's delta points are not the final key's",
+                 0x100: "l‖h of the final key is not l‖h of the origin over the ratio of their delta2"}      # VIMZ_KEYCHAIN_*
+KEYCHAIN_PLACES = (None, "the origin key's delta point", "the final key's delta point", "record", "the origin key's l‖h point", "the final key's l‖h point",
+                   "word of the fixed part")      # first_bad[0]: VIMZ_KEYCHAIN_AT_*
+KEYCHAIN_RECORD_BYTES = 296
+
+
+def contribute_key(ctx, blob, delta=None, nonce=None, seconds=None):
+    """vimz_decider_key_contribute: a further delta contribution to a saved key (Decider.save_key's bytes; phase 2 of a Groth16 ceremony) — delta1, delta2 times a
+    delta' drawn from the OS and forgotten, the l and h queries times 1/delta' on the GPU, every other byte copied.  Needs a context, no prover: the layout is read
+    from the blob's header.  Returns (key bytes, record): uint8 arrays, the record KEYCHAIN_RECORD_BYTES long (this project's own format: include/vimz_hip.h) — keep
+    the records of a chain one after another, verify_key_contributions takes them.  delta and nonce (ints, both or neither) select the TEST hook of
+    libvimz_hip_testing.so.  seconds: a list that receives [host, device, total].  VimzError(ERR_INVALID): not a key, a coordinate not below q, a bad delta point."""
+    b = np.ascontiguousarray(np.frombuffer(bytes(blob), dtype=np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else blob, dtype=np.uint8)
+    out, rec, sec = np.zeros(b.size, dtype=np.uint8), np.zeros(37, dtype=np.uint64), (C.c_double * 3)()
+    vp = C.c_void_p
+    if (delta is None) != (nonce is None):
+        raise L.VimzError(L.ERR_INVALID, "contribute_key: delta= and nonce= go together")
+    if delta is None:
+        fn = ctx.lib.vimz_decider_key_contribute
+        fn.argtypes, args = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.POINTER(C.c_double)], (sec,)
+    else:
+        fn = _seeded(ctx, "vimz_testing_decider_key_contribute_delta")
+        fn.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp, C.POINTER(C.c_double)]
+        words = [np.frombuffer(int(x).to_bytes(32, "little"), dtype="<u8").astype(np.uint64) for x in (delta, nonce)]
+        args = (_ptr(words[0]), _ptr(words[1]), sec)
+    fn.restype = C.c_int64
+    got = fn(ctx.h, _ptr(b), b.size, _ptr(out), out.size, _ptr(rec), *args)
+    if got != b.size:
+        ctx._chk(int(got) if got < 0 else L.ERR_INVALID)
+    if seconds is not None:
+        seconds[:] = list(sec)
+    return out, rec.view(np.uint8)
+
+
+def verify_key_contributions(ctx, origin, final, records, seconds=None):
+    """vimz_decider_key_verify_contributions: is `final` the key `origin` after the contributions of `records` (bytes, KEYCHAIN_RECORD_BYTES each, in order; may be
+    empty)?  Returns (bits, first_bad): bits 0 = accepted, otherwise a union of KEYCHAIN_BITS; first_bad = (place — KEYCHAIN_PLACES names it —, index).  A verified
+    chain means the final key is sound if the origin is and any ONE contributor forgot their delta'.  seconds: a list that receives [host conversion and point checks,
+    per-point flags, combination, equations].  VimzError(ERR_INVALID): a key or a record with the wrong magic or length."""
+    as_u8 = lambda x: np.ascontiguousarray(np.frombuffer(bytes(x), dtype=np.uint8) if isinstance(x, (bytes, bytearray, memoryview)) else x, dtype=np.uint8).reshape(-1)      # noqa: E731
+    o, f, r = as_u8(origin), as_u8(final), as_u8(records)
+    if r.size % KEYCHAIN_RECORD_BYTES:
+        raise L.VimzError(L.ERR_INVALID, f"verify_key_contributions: records are {KEYCHAIN_RECORD_BYTES} bytes each, not {r.size} in all")
+    vp = C.c_void_p
+    result, first, sec = C.c_uint32(0), np.zeros(2, dtype=np.uint64), (C.c_double * 4)()
+    fn = ctx.lib.vimz_decider_key_verify_contributions
+    fn.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_uint32), vp, C.POINTER(C.c_double)]
+    ctx._chk(fn(ctx.h, _ptr(o), o.size, _ptr(f), f.size, _ptr(r) if r.size else None, r.size // KEYCHAIN_RECORD_BYTES, C.byref(result), _ptr(first), sec))
+    if seconds is not None:
+        seconds[:] = list(sec)
+    return int(result.value), (int(first[0]), int(first[1]))
+
+
+def keychain_problems(bits):
+    """the names of a chain verdict's bits"""
+    return [name for bit, name in KEYCHAIN_BITS.items() if bits & bit]
+
+
 def set_head_rows(rows):
     """vimz_set_head_rows: rows of a short fold call whose Poseidon chains run on the host (0: all on the GPU; -1: the library's policy)."""
     lib = L.lib()

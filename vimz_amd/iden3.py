@@ -189,19 +189,73 @@ def _verify(argv):
     return 1
 
 
+def _contribute(argv):
+    """contribute IN.key OUT.key RECORDS: one further delta contribution to a saved decider key on GPU 0 (hip.contribute_key: delta' is drawn here and forgotten);
+    the contributed key goes to OUT.key and the 296-byte record is APPENDED to RECORDS (this project's own format, not snarkjs's .zkey)."""
+    if len(argv) != 4:
+        print(USAGE, file=sys.stderr)
+        return 2
+    from . import hip
+    blob = np.fromfile(argv[1], dtype=np.uint8)
+    sec = [0.0] * 3
+    ctx = hip.Context(0)
+    try:
+        out, rec = hip.contribute_key(ctx, blob, seconds=sec)
+    finally:
+        ctx.close()
+    with open(argv[2], "wb") as fp:
+        out.tofile(fp)
+    with open(argv[3], "ab") as fp:
+        fp.write(rec.tobytes())
+        n = fp.tell() // hip.KEYCHAIN_RECORD_BYTES
+    print(f"contribute: {argv[1]} -> {argv[2]} ({out.size} bytes), record {n} appended to {argv[3]} (host {sec[0]:.3f} s, device {sec[1]:.3f} s)")
+    return 0
+
+
+def _verify_contributions(argv):
+    """verify-contributions ORIGIN.key FINAL.key RECORDS: judges the chain on GPU 0 (hip.verify_key_contributions), prints the verdict and the times; exit status 0
+    accepted, 1 refused.  Accepted means: FINAL.key is sound if ORIGIN.key is and any one contributor forgot their delta'."""
+    if len(argv) != 4:
+        print(USAGE, file=sys.stderr)
+        return 2
+    from . import hip
+    origin, final, records = (np.fromfile(a, dtype=np.uint8) for a in argv[1:4])
+    sec = [0.0] * 4
+    ctx = hip.Context(0)
+    try:
+        bits, first = hip.verify_key_contributions(ctx, origin, final, records, seconds=sec)
+    finally:
+        ctx.close()
+    what = f"{argv[2]} after {records.size // hip.KEYCHAIN_RECORD_BYTES} contributions to {argv[1]}"
+    times = f"host conversion {sec[0]:.3f} s, per-point flags {sec[1]:.3f} s, combination {sec[2]:.3f} s, equations {sec[3]:.3f} s"
+    if not bits:
+        print(f"verify-contributions: {what}: accepted ({times})")
+        return 0
+    at = f"; first: {hip.KEYCHAIN_PLACES[first[0]]} {first[1]}" if first[0] else ""
+    print(f"verify-contributions: {what}: REFUSED (0x{bits:x}): " + "; ".join(hip.keychain_problems(bits)) + f"{at} ({times})")
+    return 1
+
+
 USAGE = ("usage: python -m vimz_amd.iden3 lagrange FILE.ptau LOGN OUT.npz\n"
          "       python -m vimz_amd.iden3 decider-key FILE.ptau TRANSFORMATION RESOLUTION OUT.key [--light] [--verify]\n"
-         "       python -m vimz_amd.iden3 verify FILE.ptau [POINTS]")
+         "       python -m vimz_amd.iden3 verify FILE.ptau [POINTS]\n"
+         "       python -m vimz_amd.iden3 contribute IN.key OUT.key RECORDS\n"
+         "       python -m vimz_amd.iden3 verify-contributions ORIGIN.key FINAL.key RECORDS")
 
 
 def _main(argv):
     """python -m vimz_amd.iden3 lagrange FILE.ptau LOGN OUT.npz: the string's Lagrange bases over the domain of 2^LOGN points (hip.lagrange_from_powers, on GPU 0)
     as an .npz of tau_g1, alpha_g1, beta_g1 (n, 8) and tau_g2 (n, 16) in the file's Montgomery form, with logn.
-    python -m vimz_amd.iden3 decider-key ...: _decider_key.  python -m vimz_amd.iden3 verify ...: _verify."""
+    python -m vimz_amd.iden3 decider-key ...: _decider_key.  python -m vimz_amd.iden3 verify ...: _verify.
+    python -m vimz_amd.iden3 contribute ... / verify-contributions ...: _contribute, _verify_contributions."""
     if argv and argv[0] == "decider-key":
         return _decider_key(argv)
     if argv and argv[0] == "verify":
         return _verify(argv)
+    if argv and argv[0] == "contribute":
+        return _contribute(argv)
+    if argv and argv[0] == "verify-contributions":
+        return _verify_contributions(argv)
     if len(argv) != 4 or argv[0] != "lagrange":
         print(USAGE, file=sys.stderr)
         return 2
