@@ -137,6 +137,36 @@ int vimz_test_decider_chains(vimz_ctx* ctx, int where, const uint64_t* gens_xy, 
  * the host (chains_on_gpu = 0) or from the device.  Returns the byte size (copies when buf is large enough); negative: vimz_decider_prove's error codes. */
 int64_t vimz_testing_decider_witness(vimz_decider* d, vimz_cf* ivc, int chains_on_gpu, void* buf, size_t cap);
 
+/* The compressed proof's kernels (vimz_amd/csrc/spartan.hip) on a caller's vectors, through the functions spartan_prove and ipa_prove run for every round
+ * (tests/test_gpu_spartan_kernels.py).  field = VIMZ_FIELD_BN254_FR or _FQ, curve = VIMZ_CURVE_BN254_G1 or _GRUMPKIN (anything else: VIMZ_ERR_INVALID); elements are
+ * canonical on both sides, 4 words each, points canonical affine, 8 words, the identity as zeros; an element not below its modulus: VIMZ_ERR_INVALID.
+ * _eq: table_out[0 .. 2^k) = eq(point, ·), point[0] the top bit of the index, 1 <= k <= 21 (eq_build: k_eq_step level by level).
+ * _sumcheck: k rounds over vectors of 2^k elements, 1 <= k <= 21, round j bound at challenges[j] (any field element).  kind = 0, the outer check: vecs = {eq, a, b,
+ * c, e}, e NULL for a strict instance; msgs_out: 3 elements a round (the evaluations at 0, 2, 3 of sum eq·(a·b − u·c − e)); finals_out: the 5 bound elements (e's
+ * zero when absent).  kind = 1, the inner check: vecs = {m, z}; 2 elements a round (evaluations at 0, 2 of sum m·z); finals_out: 2 elements.
+ * _ipa_vec: the vector side of k IPA rounds over a, b of 2^k elements: dots_out 2 elements a round (<a_L,b_R>, <a_R,b_L>), then a' = x·a_L + a_R,
+ * b' = b_L + x·b_R at challenges[j]; finals_out: a, b.
+ * _fold_bases: out_i = P_i + x·P_(i+half) over 2·half >= 2 points on the curve, x = x128[0] + 2^64·x128[1] (k_ipa_fold_bases). */
+int vimz_test_spartan_eq(vimz_ctx* ctx, int field, const uint64_t* point, size_t k, uint64_t* table_out);
+int vimz_test_spartan_sumcheck(vimz_ctx* ctx, int field, int kind, size_t k, const uint64_t* const vecs[5], const uint64_t u[4], const uint64_t* challenges,
+                               uint64_t* msgs_out, uint64_t* finals_out);
+int vimz_test_spartan_ipa_vec(vimz_ctx* ctx, int field, size_t k, const uint64_t* a, const uint64_t* b, const uint64_t* challenges, uint64_t* dots_out,
+                              uint64_t finals_out[8]);
+int vimz_test_spartan_fold_bases(vimz_ctx* ctx, int curve, const uint64_t* points_xy, size_t half, const uint64_t x128[2], uint64_t* out_xy);
+/* spartan_prove for ONE relaxed instance over a caller's R1CS: triplets as vimz_r1cs_upload takes them (canonical values) of n_c >= 2 rows and n_w >= 4 columns over
+ * the curve's scalar field; Z: n_w elements (u at wire 0, X0 and X1 at the last two); E: n_c elements, or NULL for a strict instance; ck: a key on `curve` of at least
+ * next_pow2(max(n_w, n_c)) points (shorter, or a shape below those sizes: VIMZ_ERR_INVALID).  The forward products are the seam's k_spmv3 / k_spmv_long on the uploaded
+ * shape, the transpose build_transpose's, the inner-product generator derive_ipa_u's; W' and E are committed with the library's MSM; the transcript starts from
+ * Transcript(label).  buf receives cW, cE (8 words each, cE zeros without E), then the argument's words.  Returns the byte size (copies when cap suffices), or a
+ * negative error code.
+ * _verify: the product's spartan_verify over the same shape on the caller's instance — inst = cW, cE (8 words each), u, X0, X1 (4 words each) — and argument words
+ * (both possibly tampered with).  Returns 1 (accepted), 0 (rejected) or a negative error code. */
+int64_t vimz_test_spartan_instance(vimz_ctx* ctx, int curve, size_t n_c, size_t n_w, const vimz_coo* A, const vimz_coo* B, const vimz_coo* C, const uint64_t* Z,
+                                   const uint64_t* E, const vimz_bases* ck, const uint64_t digest[4], uint32_t side_tag, const char* label, void* buf, size_t cap);
+int vimz_test_spartan_instance_verify(vimz_ctx* ctx, int curve, size_t n_c, size_t n_w, const vimz_coo* A, const vimz_coo* B, const vimz_coo* C, const vimz_bases* ck,
+                                      const uint64_t digest[4], uint32_t side_tag, const char* label, const uint64_t inst[28], int has_E, const uint64_t* words,
+                                      size_t n_words);
+
 #ifdef __cplusplus
 }
 #endif

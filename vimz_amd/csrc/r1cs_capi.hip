@@ -16,18 +16,9 @@
 
 #include "internal.hpp"
 #include "r1cs_ops.hpp"
+#include "r1cs_handle.hpp"
 
 using namespace vz;
-
-struct vimz_r1cs {
-  int field = 0;
-  size_t nrows = 0, ncols = 0, nnz[3] = {0, 0, 0};
-  CsrDev M[3] = {};
-  uint32_t* dict = nullptr; size_t ndict = 0;
-  uint32_t* long_items = nullptr; uint32_t n_long = 0, n_med = 0;
-  uint32_t* scratch = nullptr;          // 6 x nrows elements: (A,B,C)·z1 and (A,B,C)·z2 of commit_T
-  std::vector<void*> owned;
-};
 
 #define R_TRY(x) do { hipError_t _e = (x); if (_e != hipSuccess) return vz_fail(ctx, VIMZ_ERR_HIP, #x, _e); } while (0)
 

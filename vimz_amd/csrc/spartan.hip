@@ -185,6 +185,16 @@ struct SpartanCache { SideDev side[2]; std::vector<void*> owned; MsmWorkspace ws
 
 constexpr unsigned RED_BLOCKS = 512;
 
+// scratch of one side for padded shapes of up to `big` = max(M, N) elements
+hipError_t side_alloc(SideDev& S, size_t big, std::vector<void*>& owned) {
+  hipError_t e;
+  uint32_t** vecs[] = {&S.eq, &S.va, &S.vb, &S.vc, &S.ve, &S.vm, &S.vz};
+  for (auto pv : vecs) { if ((e = hipMalloc((void**)pv, 32 * big)) != hipSuccess) return e; owned.push_back(*pv); }
+  if ((e = hipMalloc((void**)&S.G, 4 * (size_t)AFFINE_WORDS * big)) != hipSuccess) return e; owned.push_back(S.G);
+  if ((e = hipMalloc((void**)&S.partial, 32 * 3 * (RED_BLOCKS + 1))) != hipSuccess) return e; owned.push_back(S.partial);
+  return hipHostMalloc((void**)&S.pin, 32 * 8);
+}
+
 uint32_t ceil_log2(size_t x) { uint32_t k = 0; while (((size_t)1 << k) < x) k++; return k; }
 
 template <class F>
@@ -278,11 +288,7 @@ int spartan_setup(vimz_ivc* v, SpartanCache** out) {
     S.s = ceil_log2(S.n_c); S.t = ceil_log2(S.n_w); S.M = (size_t)1 << S.s; S.N = (size_t)1 << S.t;
     const size_t big = std::max(S.M, S.N);
     if ((side == 0 ? v->ck1->n : v->ck2->n) < big) return vz_fail(ctx, VIMZ_ERR_INVALID, "compress: the commitment key is shorter than the padded shape (needs next_pow2(max(wires, constraints)) generators)");
-    uint32_t** vecs[] = {&S.eq, &S.va, &S.vb, &S.vc, &S.ve, &S.vm, &S.vz};
-    for (auto pv : vecs) { P_TRY(hipMalloc((void**)pv, 32 * big)); c->owned.push_back(*pv); }
-    P_TRY(hipMalloc((void**)&S.G, 4 * (size_t)AFFINE_WORDS * big)); c->owned.push_back(S.G);
-    P_TRY(hipMalloc((void**)&S.partial, 32 * 3 * (RED_BLOCKS + 1))); c->owned.push_back(S.partial);
-    P_TRY(hipHostMalloc((void**)&S.pin, 32 * 8));
+    P_TRY(side_alloc(S, big, c->owned));
   }
   *out = c.get();
   v->spartan_cache = c.release();
@@ -321,6 +327,74 @@ void absorb_instance(Transcript& tr, const F& digest, const Instance<F, FS>& I, 
   tr.absorb_fe("u", I.u); tr.absorb_fe("X0", I.X0); tr.absorb_fe("X1", I.X1);
 }
 
+// ---- the bodies of the prover's loops (spartan_prove / ipa_prove and the test hooks of include/vimz_hip_testing.h run these very functions) --------
+// tab[0 .. 2^k) = eq(pt, ·), pt[0] = the top bit of the index
+template <class F>
+hipError_t eq_build(hipStream_t s, uint32_t* tab, const std::vector<F>& pt) {
+  const F one = F::one();
+  hipError_t e;
+  if ((e = hipMemcpyAsync(tab, one.v, 32, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
+  if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+  const uint32_t k = (uint32_t)pt.size();
+  for (uint32_t q = k; q-- > 0;) hipLaunchKernelGGL(k_eq_step<F>, dim3(stream_grid((size_t)1 << (k - 1 - q))), dim3(256), 0, s, tab, (size_t)1 << (k - 1 - q), pt[q]);
+  return hipSuccess;
+}
+
+inline unsigned red_grid(size_t half) { return (unsigned)std::min<size_t>(RED_BLOCKS, (half + 255) / 256); }
+
+// one outer round over eq, va, vb, vc (ve) of 2·half elements: the three evaluations, `next(s0, s2, s3)` -> the round's challenge r, then the bind at r
+template <class F, class Next>
+hipError_t outer_round(SideDev& S, hipStream_t s, size_t half, bool has_E, const F& u, Next next) {
+  const unsigned gb = red_grid(half);
+  hipLaunchKernelGGL(k_sc_outer<F>, dim3(gb), dim3(256), 0, s, (const uint32_t*)S.eq, (const uint32_t*)S.va, (const uint32_t*)S.vb, (const uint32_t*)S.vc,
+                     has_E ? (const uint32_t*)S.ve : (const uint32_t*)nullptr, half, u, S.partial);
+  hipLaunchKernelGGL((k_sum_partials<F, 3>), dim3(1), dim3(256), 0, s, (const uint32_t*)S.partial, gb, S.partial + 8 * 3 * RED_BLOCKS);
+  hipError_t e;
+  if ((e = hipMemcpyAsync(S.pin, S.partial + 8 * 3 * RED_BLOCKS, 96, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+  if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+  F s0, s2, s3; memcpy(s0.v, S.pin, 32); memcpy(s2.v, S.pin + 8, 32); memcpy(s3.v, S.pin + 16, 32);
+  const F r = next(s0, s2, s3);
+  BindSet bs{{S.eq, S.va, S.vb, S.vc, has_E ? S.ve : nullptr}, 5};
+  hipLaunchKernelGGL(k_bind<F>, dim3(stream_grid(half)), dim3(256), 0, s, bs, half, r);
+  return hipSuccess;
+}
+
+// one inner round over vm, vz: the two evaluations, `next(s0, s2)` -> r, then the bind
+template <class F, class Next>
+hipError_t inner_round(SideDev& S, hipStream_t s, size_t half, Next next) {
+  const unsigned gb = red_grid(half);
+  hipLaunchKernelGGL(k_sc_inner<F>, dim3(gb), dim3(256), 0, s, (const uint32_t*)S.vm, (const uint32_t*)S.vz, half, S.partial);
+  hipLaunchKernelGGL((k_sum_partials<F, 2>), dim3(1), dim3(256), 0, s, (const uint32_t*)S.partial, gb, S.partial + 8 * 3 * RED_BLOCKS);
+  hipError_t e;
+  if ((e = hipMemcpyAsync(S.pin, S.partial + 8 * 3 * RED_BLOCKS, 64, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+  if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+  F s0, s2; memcpy(s0.v, S.pin, 32); memcpy(s2.v, S.pin + 8, 32);
+  const F r = next(s0, s2);
+  BindSet bs{{S.vm, S.vz, nullptr, nullptr, nullptr}, 2};
+  hipLaunchKernelGGL(k_bind<F>, dim3(stream_grid(half)), dim3(256), 0, s, bs, half, r);
+  return hipSuccess;
+}
+
+// the vector side of one IPA round over a, b of 2·half elements: (<a_L,b_R>, <a_R,b_L>) queued into the pinned buffer, then `next(pin, &x)` — which must
+// synchronise the stream before it reads the two elements (the prover's MSMs do) — gives the challenge, then the fold of a and b
+template <class F, class Next>
+hipError_t ipa_vec_round(SideDev& S, hipStream_t s, uint32_t* a, uint32_t* b, size_t half, Next next) {
+  const unsigned gb = red_grid(half);
+  hipLaunchKernelGGL(k_dot2<F>, dim3(gb), dim3(256), 0, s, (const uint32_t*)a, (const uint32_t*)b, half, S.partial);
+  hipLaunchKernelGGL((k_sum_partials<F, 2>), dim3(1), dim3(256), 0, s, (const uint32_t*)S.partial, gb, S.partial + 8 * 3 * RED_BLOCKS);
+  hipError_t e;
+  if ((e = hipMemcpyAsync(S.pin, S.partial + 8 * 3 * RED_BLOCKS, 64, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+  F x;
+  if ((e = next((const uint32_t*)S.pin, &x)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_ipa_fold_vec<F>, dim3(stream_grid(half)), dim3(256), 0, s, a, b, half, x);
+  return hipSuccess;
+}
+
+template <class G>
+void ipa_fold_bases(hipStream_t s, uint32_t* bases, size_t half, const uint32_t xw[4]) {
+  hipLaunchKernelGGL(k_ipa_fold_bases<G>, dim3(stream_grid(half)), dim3(256), 0, s, bases, half, make_uint4(xw[0], xw[1], xw[2], xw[3]));
+}
+
 // ---- prover ----------------------------------------------------------------------------------------------------------------------------
 template <class F, class C>
 int ipa_prove(vimz_ctx* ctx, SpartanCache& cache, SideDev& S, hipStream_t s, Transcript& tr, const Affine<typename C::Base>& Ugen, uint32_t* a, uint32_t* b,
@@ -333,24 +407,25 @@ int ipa_prove(vimz_ctx* ctx, SpartanCache& cache, SideDev& S, hipStream_t s, Tra
   size_t len = (size_t)1 << rounds;
   for (uint32_t j = 0; j < rounds; j++) {
     const size_t half = len >> 1;
-    const unsigned gb = (unsigned)std::min<size_t>(RED_BLOCKS, (half + 255) / 256);
-    hipLaunchKernelGGL(k_dot2<F>, dim3(gb), dim3(256), 0, s, (const uint32_t*)a, (const uint32_t*)b, half, S.partial);
-    hipLaunchKernelGGL((k_sum_partials<F, 2>), dim3(1), dim3(256), 0, s, (const uint32_t*)S.partial, gb, S.partial + 8 * 3 * RED_BLOCKS);
-    P_TRY(hipMemcpyAsync(S.pin, S.partial + 8 * 3 * RED_BLOCKS, 64, hipMemcpyDeviceToHost, s));
-    Affine<FS> Lg, Rg;
-    P_TRY(msm_run<C>(s, cache.ws, S.G + (size_t)AFFINE_WORDS * half, a, half, 1, 0, &Lg, nullptr, nullptr, 0, nullptr));          // <a_L, G_R>
-    P_TRY(msm_run<C>(s, cache.ws, S.G, a + 8 * half, half, 1, 0, &Rg, nullptr, nullptr, 0, nullptr));                             // <a_R, G_L>
-    F cl, cr; memcpy(cl.v, S.pin, 32); memcpy(cr.v, S.pin + 8, 32);              // (the MSMs synchronised the stream)
-    XYZZ<FS> L = from_affine(Lg); { XYZZ<FS> t = host_mul_fe<FS, F>(Up, cl); add_full(L, t); }
-    XYZZ<FS> R = from_affine(Rg); { XYZZ<FS> t = host_mul_fe<FS, F>(Up, cr); add_full(R, t); }
-    const Affine<FS> La = to_affine(L), Ra = to_affine(R);
-    out.point(La); out.point(Ra);
-    tr.absorb_fe("L.x", La.x); tr.absorb_fe("L.y", La.y); tr.absorb_fe("R.x", Ra.x); tr.absorb_fe("R.y", Ra.y);
-    uint32_t xw[4]; tr.challenge(xw);
-    F xc = F::zero(); for (int k = 0; k < 4; k++) xc.v[k] = xw[k];
-    const F x = F::to_mont(xc);
-    hipLaunchKernelGGL(k_ipa_fold_vec<F>, dim3(stream_grid(half)), dim3(256), 0, s, a, b, half, x);
-    hipLaunchKernelGGL(k_ipa_fold_bases<G>, dim3(stream_grid(half)), dim3(256), 0, s, S.G, half, make_uint4(xw[0], xw[1], xw[2], xw[3]));
+    uint32_t xw[4];
+    auto group_side = [&](const uint32_t* pin, F* x) -> hipError_t {
+      hipError_t e;
+      Affine<FS> Lg, Rg;
+      if ((e = msm_run<C>(s, cache.ws, S.G + (size_t)AFFINE_WORDS * half, a, half, 1, 0, &Lg, nullptr, nullptr, 0, nullptr)) != hipSuccess) return e;          // <a_L, G_R>
+      if ((e = msm_run<C>(s, cache.ws, S.G, a + 8 * half, half, 1, 0, &Rg, nullptr, nullptr, 0, nullptr)) != hipSuccess) return e;                             // <a_R, G_L>
+      F cl, cr; memcpy(cl.v, pin, 32); memcpy(cr.v, pin + 8, 32);              // (the MSMs synchronised the stream)
+      XYZZ<FS> L = from_affine(Lg); { XYZZ<FS> t = host_mul_fe<FS, F>(Up, cl); add_full(L, t); }
+      XYZZ<FS> R = from_affine(Rg); { XYZZ<FS> t = host_mul_fe<FS, F>(Up, cr); add_full(R, t); }
+      const Affine<FS> La = to_affine(L), Ra = to_affine(R);
+      out.point(La); out.point(Ra);
+      tr.absorb_fe("L.x", La.x); tr.absorb_fe("L.y", La.y); tr.absorb_fe("R.x", Ra.x); tr.absorb_fe("R.y", Ra.y);
+      tr.challenge(xw);
+      F xc = F::zero(); for (int k = 0; k < 4; k++) xc.v[k] = xw[k];
+      *x = F::to_mont(xc);
+      return hipSuccess;
+    };
+    P_TRY(ipa_vec_round<F>(S, s, a, b, half, group_side));
+    ipa_fold_bases<G>(s, S.G, half, xw);
     P_TRY(hipGetLastError());
     len = half;
   }
@@ -384,28 +459,21 @@ int spartan_prove(vimz_ctx* ctx, SpartanCache& cache, SideDev& S, hipStream_t s,
   // eq(tau, ·)
   std::vector<F> tau(S.s);
   for (auto& x : tau) x = tr.challenge_fe<F>();
-  { const F one = F::one(); P_TRY(hipMemcpyAsync(S.eq, one.v, 32, hipMemcpyHostToDevice, s)); P_TRY(hipStreamSynchronize(s)); }
-  for (uint32_t k = S.s; k-- > 0;) hipLaunchKernelGGL(k_eq_step<F>, dim3(stream_grid((size_t)1 << (S.s - 1 - k))), dim3(256), 0, s, S.eq, (size_t)1 << (S.s - 1 - k), tau[k]);
+  P_TRY(eq_build<F>(s, S.eq, tau));
   // outer sum-check
   F claim = F::zero();
   std::vector<F> rx(S.s);
   size_t len = M;
   for (uint32_t j = 0; j < S.s; j++) {
     const size_t half = len >> 1;
-    const unsigned gb = (unsigned)std::min<size_t>(RED_BLOCKS, (half + 255) / 256);
-    hipLaunchKernelGGL(k_sc_outer<F>, dim3(gb), dim3(256), 0, s, (const uint32_t*)S.eq, (const uint32_t*)S.va, (const uint32_t*)S.vb, (const uint32_t*)S.vc,
-                       E ? (const uint32_t*)S.ve : (const uint32_t*)nullptr, half, I.u, S.partial);
-    hipLaunchKernelGGL((k_sum_partials<F, 3>), dim3(1), dim3(256), 0, s, (const uint32_t*)S.partial, gb, S.partial + 8 * 3 * RED_BLOCKS);
-    P_TRY(hipMemcpyAsync(S.pin, S.partial + 8 * 3 * RED_BLOCKS, 96, hipMemcpyDeviceToHost, s));
-    P_TRY(hipStreamSynchronize(s));
-    F s0, s2, s3; memcpy(s0.v, S.pin, 32); memcpy(s2.v, S.pin + 8, 32); memcpy(s3.v, S.pin + 16, 32);
-    out.fe(s0); out.fe(s2); out.fe(s3);
-    tr.absorb_fe("o0", s0); tr.absorb_fe("o2", s2); tr.absorb_fe("o3", s3);
-    const F r = tr.challenge_fe<F>();
-    rx[j] = r;
-    claim = interp_cubic(s0, F::sub(claim, s0), s2, s3, r);
-    BindSet bs{{S.eq, S.va, S.vb, S.vc, E ? S.ve : nullptr}, 5};
-    hipLaunchKernelGGL(k_bind<F>, dim3(stream_grid(half)), dim3(256), 0, s, bs, half, r);
+    P_TRY(outer_round<F>(S, s, half, E != nullptr, I.u, [&](const F& s0, const F& s2, const F& s3) {
+      out.fe(s0); out.fe(s2); out.fe(s3);
+      tr.absorb_fe("o0", s0); tr.absorb_fe("o2", s2); tr.absorb_fe("o3", s3);
+      const F r = tr.challenge_fe<F>();
+      rx[j] = r;
+      claim = interp_cubic(s0, F::sub(claim, s0), s2, s3, r);
+      return r;
+    }));
     len = half;
   }
   F cl[4];
@@ -417,8 +485,7 @@ int spartan_prove(vimz_ctx* ctx, SpartanCache& cache, SideDev& S, hipStream_t s,
   for (int k = 0; k < 4; k++) { out.fe(cl[k]); tr.absorb_fe("claim", cl[k]); }
   const F rho = tr.challenge_fe<F>(), rho2 = F::sqr(rho);
   // eq(rx, ·) over the rows, then M = A^T e + rho B^T e + rho^2 C^T e over the columns
-  { const F one = F::one(); P_TRY(hipMemcpyAsync(S.eq, one.v, 32, hipMemcpyHostToDevice, s)); P_TRY(hipStreamSynchronize(s)); }
-  for (uint32_t k = S.s; k-- > 0;) hipLaunchKernelGGL(k_eq_step<F>, dim3(stream_grid((size_t)1 << (S.s - 1 - k))), dim3(256), 0, s, S.eq, (size_t)1 << (S.s - 1 - k), rx[k]);
+  P_TRY(eq_build<F>(s, S.eq, rx));
   spmv_any<F>(s, S.At, S.Bt, S.Ct, S.dict, S.items_t, S.n_long_t, S.n_med_t, S.n_w, S.eq, S.va, S.vb, S.vc);
   P_TRY(hipMemsetAsync(S.vm, 0, 32 * big, s)); P_TRY(hipMemsetAsync(S.vz, 0, 32 * big, s));
   hipLaunchKernelGGL(k_combine3<F>, dim3(stream_grid(S.n_w)), dim3(256), 0, s, (size_t)S.n_w, (const uint32_t*)S.va, (const uint32_t*)S.vb, (const uint32_t*)S.vc, rho, rho2, S.vm);
@@ -428,19 +495,14 @@ int spartan_prove(vimz_ctx* ctx, SpartanCache& cache, SideDev& S, hipStream_t s,
   len = N;
   for (uint32_t j = 0; j < S.t; j++) {
     const size_t half = len >> 1;
-    const unsigned gb = (unsigned)std::min<size_t>(RED_BLOCKS, (half + 255) / 256);
-    hipLaunchKernelGGL(k_sc_inner<F>, dim3(gb), dim3(256), 0, s, (const uint32_t*)S.vm, (const uint32_t*)S.vz, half, S.partial);
-    hipLaunchKernelGGL((k_sum_partials<F, 2>), dim3(1), dim3(256), 0, s, (const uint32_t*)S.partial, gb, S.partial + 8 * 3 * RED_BLOCKS);
-    P_TRY(hipMemcpyAsync(S.pin, S.partial + 8 * 3 * RED_BLOCKS, 64, hipMemcpyDeviceToHost, s));
-    P_TRY(hipStreamSynchronize(s));
-    F s0, s2; memcpy(s0.v, S.pin, 32); memcpy(s2.v, S.pin + 8, 32);
-    out.fe(s0); out.fe(s2);
-    tr.absorb_fe("i0", s0); tr.absorb_fe("i2", s2);
-    const F r = tr.challenge_fe<F>();
-    ry[j] = r;
-    claim = interp_quad(s0, F::sub(claim, s0), s2, r);
-    BindSet bs{{S.vm, S.vz, nullptr, nullptr, nullptr}, 2};
-    hipLaunchKernelGGL(k_bind<F>, dim3(stream_grid(half)), dim3(256), 0, s, bs, half, r);
+    P_TRY(inner_round<F>(S, s, half, [&](const F& s0, const F& s2) {
+      out.fe(s0); out.fe(s2);
+      tr.absorb_fe("i0", s0); tr.absorb_fe("i2", s2);
+      const F r = tr.challenge_fe<F>();
+      ry[j] = r;
+      claim = interp_quad(s0, F::sub(claim, s0), s2, r);
+      return r;
+    }));
     len = half;
   }
   // Z(ry) is what the bound vector holds; the committed part's evaluation is Z(ry) minus the three public entries' share
@@ -460,8 +522,7 @@ int spartan_prove(vimz_ctx* ctx, SpartanCache& cache, SideDev& S, hipStream_t s,
   // opening of the committed part of Z at ry:  a = W' (into va), b = eq(ry, ·) (into vb), bases shifted by one wire
   int rc;
   hipLaunchKernelGGL(k_committed_part<F>, dim3(stream_grid(N)), dim3(256), 0, s, Z, (size_t)S.n_w, N, S.va);
-  { const F one = F::one(); P_TRY(hipMemcpyAsync(S.vb, one.v, 32, hipMemcpyHostToDevice, s)); P_TRY(hipStreamSynchronize(s)); }
-  for (uint32_t k = S.t; k-- > 0;) hipLaunchKernelGGL(k_eq_step<F>, dim3(stream_grid((size_t)1 << (S.t - 1 - k))), dim3(256), 0, s, S.vb, (size_t)1 << (S.t - 1 - k), ry[k]);
+  P_TRY(eq_build<F>(s, S.vb, ry));
   hipLaunchKernelGGL(k_mask_public<F>, dim3(stream_grid(N)), dim3(256), 0, s, S.vb, (size_t)S.n_w, N);
   if (forge_public_slot) {      // test hook (vimz_ivc_compress): the opened vector carries X0 − X0' = −1 in the slot of wire n−2
     const F m1 = F::neg(F::one());
@@ -473,8 +534,7 @@ int spartan_prove(vimz_ctx* ctx, SpartanCache& cache, SideDev& S, hipStream_t s,
   if (E) {
     P_TRY(hipMemsetAsync(S.va, 0, 32 * M, s));
     P_TRY(hipMemcpyAsync(S.va, E, 32 * (size_t)S.n_c, hipMemcpyDeviceToDevice, s));
-    { const F one = F::one(); P_TRY(hipMemcpyAsync(S.vb, one.v, 32, hipMemcpyHostToDevice, s)); P_TRY(hipStreamSynchronize(s)); }
-    for (uint32_t k = S.s; k-- > 0;) hipLaunchKernelGGL(k_eq_step<F>, dim3(stream_grid((size_t)1 << (S.s - 1 - k))), dim3(256), 0, s, S.vb, (size_t)1 << (S.s - 1 - k), rx[k]);
+    P_TRY(eq_build<F>(s, S.vb, rx));
     P_TRY(load_bases(s, S.G, ck, M, false));
     if ((rc = ipa_prove<F, C>(ctx, cache, S, s, tr, Ugen, S.va, S.vb, S.s, I.cE, cl[3], out))) return rc;
   }
@@ -633,8 +693,6 @@ extern "C" {
 size_t vimz_ivc_compressed_size(vimz_ivc* v) {
   if (!v) return 0;
   const uint32_t s1 = ceil_log2(v->pri->n_c), t1 = ceil_log2(v->pri->n_wires), s2 = ceil_log2(v->sec.n_c), t2 = ceil_log2(v->sec.n_w);
-  auto snark = [](size_t s, size_t t, bool e) { return 4 * (3 * s + 4 + 2 * t + 1 + (4 * t + 1) * 2 / 2 + (e ? 4 * s + 1 : 0)) + 4 * (4 * t); };
-  (void)snark;
   auto words = [](size_t s, size_t t, bool e) { return 4 * (3 * s + 4 + 2 * t + 1) + 4 * (4 * t + 1) + (e ? 4 * (4 * s + 1) : 0); };
   return 8 * (8 + 4 * 2 * (size_t)v->pri->len_z + 4 * (7 + 7 + 4) + words(s1, t1, true) + words(s2, t2, true) + words(s2, t2, false));
 }
@@ -853,3 +911,329 @@ int vimz_ivc_verify_merged_compressed(vimz_ivc* v, const uint8_t* blob, size_t l
 }
 
 }  // extern "C"
+
+#ifdef VIMZ_TESTING
+// ---- test hooks (include/vimz_hip_testing.h): in libvimz_hip_testing.so only.  Every launch below goes through the functions the prover runs. ----------------
+#include "r1cs_handle.hpp"
+
+namespace {
+
+struct TestSide {          // one side's scratch (and, for a whole instance, its shape) for the length of a hook
+  SpartanCache cache;
+  SideDev& S = cache.side[0];
+  ~TestSide() { for (void* d : cache.owned) hipFree(d); if (S.pin) hipHostFree(S.pin); cache.ws.release(); }
+};
+
+template <class F>
+bool canon_in(const uint64_t* src, size_t n, std::vector<F>& out) {        // canonical words -> Montgomery elements; false: one is not below the modulus
+  out.resize(n);
+  for (size_t i = 0; i < n; i++) { F c; memcpy(c.v, src + 4 * i, 32); if (!c.is_reduced()) return false; out[i] = F::to_mont(c); }
+  return true;
+}
+template <class F>
+void canon_out(uint64_t* dst, const F& mont) { const F c = F::from_mont(mont); memcpy(dst, c.v, 32); }
+
+template <class F>
+hipError_t vec_up(hipStream_t s, uint32_t* d, const std::vector<F>& v) { return hipMemcpyAsync(d, v.data(), 32 * v.size(), hipMemcpyHostToDevice, s); }
+template <class F>
+hipError_t elem_down(hipStream_t s, const uint32_t* d, F* out) {
+  hipError_t e = hipMemcpyAsync(out->v, d, 32, hipMemcpyDeviceToHost, s);
+  return e != hipSuccess ? e : hipStreamSynchronize(s);
+}
+
+template <class Fn>
+int scalar_field_dispatch(int field, Fn fn) {
+  if (field == VIMZ_FIELD_BN254_FR) return fn(Fe());
+  if (field == VIMZ_FIELD_BN254_FQ) return fn(Fq());
+  return VIMZ_ERR_INVALID;
+}
+
+template <class F>
+int test_eq(vimz_ctx* ctx, const uint64_t* point, size_t k, uint64_t* table_out) {
+  std::vector<F> pt;
+  if (!canon_in(point, k, pt)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_eq: element not below the modulus");
+  const size_t n = (size_t)1 << k;
+  TestSide T; hipStream_t s = ctx->stream;
+  P_TRY(side_alloc(T.S, n, T.cache.owned));
+  P_TRY(eq_build<F>(s, T.S.eq, pt));
+  launch_from_mont<F>(s, T.S.eq, T.S.va, n);
+  P_TRY(hipGetLastError());
+  P_TRY(hipMemcpyAsync(table_out, T.S.va, 32 * n, hipMemcpyDeviceToHost, s));
+  P_TRY(hipStreamSynchronize(s));
+  return VIMZ_OK;
+}
+
+template <class F>
+int test_sumcheck(vimz_ctx* ctx, int kind, size_t k, const uint64_t* const vecs[5], const uint64_t u[4], const uint64_t* challenges, uint64_t* msgs_out, uint64_t* finals_out) {
+  const size_t n = (size_t)1 << k;
+  const int nv = kind == 0 ? 5 : 2;
+  const bool has_E = kind == 0 && vecs[4];
+  std::vector<F> r, uu;
+  if (!canon_in(challenges, k, r) || (kind == 0 && !canon_in(u, 1, uu))) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_sumcheck: element not below the modulus");
+  TestSide T; SideDev& S = T.S; hipStream_t s = ctx->stream;
+  P_TRY(side_alloc(S, n, T.cache.owned));
+  uint32_t* dst[5] = {kind == 0 ? S.eq : S.vm, kind == 0 ? S.va : S.vz, S.vb, S.vc, S.ve};
+  {
+    std::vector<F> v;
+    for (int q = 0; q < nv; q++) {
+      if (!vecs[q]) continue;
+      if (!canon_in(vecs[q], n, v)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_sumcheck: element not below the modulus");
+      P_TRY(vec_up(s, dst[q], v));
+      P_TRY(hipStreamSynchronize(s));
+    }
+  }
+  size_t len = n;
+  for (size_t j = 0; j < k; j++) {
+    const size_t half = len >> 1;
+    if (kind == 0)
+      P_TRY(outer_round<F>(S, s, half, has_E, uu[0], [&](const F& s0, const F& s2, const F& s3) { canon_out(msgs_out + 12 * j, s0); canon_out(msgs_out + 12 * j + 4, s2); canon_out(msgs_out + 12 * j + 8, s3); return r[j]; }));
+    else
+      P_TRY(inner_round<F>(S, s, half, [&](const F& s0, const F& s2) { canon_out(msgs_out + 8 * j, s0); canon_out(msgs_out + 8 * j + 4, s2); return r[j]; }));
+    len = half;
+  }
+  P_TRY(hipGetLastError());
+  for (int q = 0; q < nv; q++) {
+    F x = F::zero();
+    if (q < 4 || has_E) P_TRY(elem_down(s, dst[q], &x));
+    canon_out(finals_out + 4 * q, x);
+  }
+  return VIMZ_OK;
+}
+
+template <class F>
+int test_ipa_vec(vimz_ctx* ctx, size_t k, const uint64_t* a, const uint64_t* b, const uint64_t* challenges, uint64_t* dots_out, uint64_t* finals_out) {
+  const size_t n = (size_t)1 << k;
+  std::vector<F> r, va, vb;
+  if (!canon_in(challenges, k, r) || !canon_in(a, n, va) || !canon_in(b, n, vb)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_ipa_vec: element not below the modulus");
+  TestSide T; SideDev& S = T.S; hipStream_t s = ctx->stream;
+  P_TRY(side_alloc(S, n, T.cache.owned));
+  P_TRY(vec_up(s, S.va, va)); P_TRY(vec_up(s, S.vb, vb));
+  P_TRY(hipStreamSynchronize(s));
+  size_t len = n;
+  for (size_t j = 0; j < k; j++) {
+    const size_t half = len >> 1;
+    auto read_dots = [&](const uint32_t* pin, F* x) -> hipError_t {
+      const hipError_t e = hipStreamSynchronize(s);
+      if (e != hipSuccess) return e;
+      F cl, cr; memcpy(cl.v, pin, 32); memcpy(cr.v, pin + 8, 32);
+      canon_out(dots_out + 8 * j, cl); canon_out(dots_out + 8 * j + 4, cr);
+      *x = r[j];
+      return hipSuccess;
+    };
+    P_TRY(ipa_vec_round<F>(S, s, S.va, S.vb, half, read_dots));
+    len = half;
+  }
+  P_TRY(hipGetLastError());
+  F fa, fb;
+  P_TRY(elem_down(s, S.va, &fa)); P_TRY(elem_down(s, S.vb, &fb));
+  canon_out(finals_out, fa); canon_out(finals_out + 4, fb);
+  return VIMZ_OK;
+}
+
+// canonical affine points (8 words each) -> Montgomery; 0: good, 1: a coordinate not below the modulus, 2: a point off the curve
+template <class FS>
+int points_in(const uint64_t* xy, size_t n, std::vector<Affine<FS>>& out) {
+  out.resize(n);
+  for (size_t i = 0; i < n; i++) {
+    FS x, y; memcpy(x.v, xy + 8 * i, 32); memcpy(y.v, xy + 8 * i + 4, 32);
+    if (!x.is_reduced() || !y.is_reduced()) return 1;
+    out[i].x = FS::to_mont(x); out[i].y = FS::to_mont(y);
+    if (!aff_on_curve(out[i])) return 2;
+  }
+  return 0;
+}
+
+template <class C>
+int test_fold_bases(vimz_ctx* ctx, const uint64_t* points_xy, size_t half, const uint64_t x128[2], uint64_t* out_xy) {
+  typedef typename C::Base FS;
+  typedef typename C::Coord G;
+  std::vector<Affine<FS>> pts;
+  if (points_in(points_xy, 2 * half, pts)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_fold_bases: a coordinate not below the modulus, or a point off the curve");
+  hipStream_t s = ctx->stream;
+  uint32_t *raw = nullptr, *gd = nullptr;
+  P_TRY(hipMalloc((void**)&raw, 64 * 2 * half));
+  hipError_t e = hipMalloc((void**)&gd, 4 * (size_t)AFFINE_WORDS * 2 * half);
+  if (e == hipSuccess) e = hipMemcpyAsync(raw, pts.data(), 64 * 2 * half, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) {
+    launch_points_to_internal<FS>(s, raw, 0, gd, 2 * half);
+    const uint32_t xw[4] = {(uint32_t)x128[0], (uint32_t)(x128[0] >> 32), (uint32_t)x128[1], (uint32_t)(x128[1] >> 32)};
+    ipa_fold_bases<G>(s, gd, half, xw);
+    launch_points_from_internal<FS>(s, gd, 1, raw, half);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out_xy, raw, 64 * half, hipMemcpyDeviceToHost, s);
+  const hipError_t e2 = hipStreamSynchronize(s);
+  hipFree(raw); hipFree(gd);
+  if (e != hipSuccess) return vz_fail(ctx, VIMZ_ERR_HIP, "vimz_test_spartan_fold_bases", e);
+  if (e2 != hipSuccess) return vz_fail(ctx, VIMZ_ERR_HIP, "vimz_test_spartan_fold_bases: synchronize", e2);
+  return VIMZ_OK;
+}
+
+// the shape of a whole-instance hook: the seam's upload for the forward side, its CSR read back for build_transpose and the verifier
+template <class F>
+struct TestShape { cb::Csr A, B, C; std::vector<F> dict; };
+
+template <class F>
+int test_side_build(vimz_ctx* ctx, const vimz_r1cs* R, const vimz_bases* ck, TestSide& T, TestShape<F>& H) {
+  SideDev& S = T.S;
+  cb::Csr* Ms[3] = {&H.A, &H.B, &H.C};
+  for (int m = 0; m < 3; m++) {
+    Ms[m]->row_ptr.assign(R->nrows + 1, 0); Ms[m]->col.resize(R->nnz[m]); Ms[m]->coef.resize(R->nnz[m]);
+    P_TRY(hipMemcpy(Ms[m]->row_ptr.data(), R->M[m].row_ptr, 4 * (R->nrows + 1), hipMemcpyDeviceToHost));
+    if (R->nnz[m]) { P_TRY(hipMemcpy(Ms[m]->col.data(), R->M[m].col, 4 * R->nnz[m], hipMemcpyDeviceToHost)); P_TRY(hipMemcpy(Ms[m]->coef.data(), R->M[m].coef, 4 * R->nnz[m], hipMemcpyDeviceToHost)); }
+  }
+  {
+    std::vector<F> dd(2 * R->ndict);
+    if (R->ndict) P_TRY(hipMemcpy(dd.data(), R->dict, 32 * dd.size(), hipMemcpyDeviceToHost));
+    H.dict.resize(R->ndict);
+    for (size_t i = 0; i < R->ndict; i++) H.dict[i] = dd[2 * i];
+  }
+  S.A = R->M[0]; S.B = R->M[1]; S.C = R->M[2]; S.dict = R->dict; S.items = R->long_items; S.n_long = R->n_long; S.n_med = R->n_med;
+  S.n_w = (uint32_t)R->ncols; S.n_c = (uint32_t)R->nrows;
+  const cb::Csr* M3[3] = {&H.A, &H.B, &H.C};
+  P_TRY(build_transpose<F>(M3, S.n_c, S.n_w, S, T.cache.owned));
+  S.s = ceil_log2(S.n_c); S.t = ceil_log2(S.n_w); S.M = (size_t)1 << S.s; S.N = (size_t)1 << S.t;
+  if (ck->n < std::max(S.M, S.N)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_instance: the commitment key is shorter than the padded shape");
+  P_TRY(side_alloc(S, std::max(S.M, S.N), T.cache.owned));
+  return VIMZ_OK;
+}
+
+template <class F, class C>
+int64_t test_instance(vimz_ctx* ctx, int curve, const vimz_r1cs* R, const uint64_t* Zc, const uint64_t* Ec, const vimz_bases* ck, const uint64_t digest[4],
+                      uint32_t side_tag, const char* label, void* buf, size_t cap) {
+  typedef typename C::Base FS;
+  std::vector<F> Z, E, dg;
+  if (!canon_in(Zc, R->ncols, Z) || (Ec && !canon_in(Ec, R->nrows, E)) || !canon_in(digest, 1, dg)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_instance: element not below the modulus");
+  Affine<FS> Ugen;
+  int rc = derive_ipa_u<C>(ctx, curve, &Ugen);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  P_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  TestSide T; TestShape<F> H; SideDev& S = T.S;
+  if ((rc = test_side_build<F>(ctx, R, ck, T, H))) return rc;
+  uint32_t *Zd = nullptr, *Ed = nullptr;
+  P_TRY(hipMalloc((void**)&Zd, 32 * Z.size())); T.cache.owned.push_back(Zd);
+  P_TRY(vec_up(s, Zd, Z));
+  if (Ec) { P_TRY(hipMalloc((void**)&Ed, 32 * E.size())); T.cache.owned.push_back(Ed); P_TRY(vec_up(s, Ed, E)); }
+  P_TRY(hipStreamSynchronize(s));
+  Instance<F, FS> I;
+  I.u = Z[0]; I.X0 = Z[S.n_w - 2]; I.X1 = Z[S.n_w - 1]; I.has_E = Ec != nullptr;
+  I.cE.x = I.cE.y = FS::zero();
+  P_TRY(msm_run<C>(s, T.cache.ws, ck->d, Zd + 8, (size_t)S.n_w - 3, 1, 0, &I.cW, nullptr, nullptr, 0, nullptr));          // wire i -> ck[i − 1], the committed wires 1 .. n_w − 3
+  if (Ec) P_TRY(msm_run<C>(s, T.cache.ws, ck->d, Ed, (size_t)S.n_c, 1, 0, &I.cE, nullptr, nullptr, 0, nullptr));
+  Transcript tr(label);
+  Writer out;
+  out.point(I.cW); out.point(I.cE);
+  auto fwd = [&](const uint32_t* z, uint32_t* az, uint32_t* bz, uint32_t* cz) { spmv_any<F>(s, S.A, S.B, S.C, S.dict, S.items, S.n_long, S.n_med, S.n_c, z, az, bz, cz); };
+  if ((rc = spartan_prove<F, C>(ctx, T.cache, S, s, ck, Ugen, dg[0], I, Zd, Ed, side_tag, tr, out, fwd))) return rc;
+  P_TRY(hipStreamSynchronize(s));
+  const size_t bytes = 8 * out.w.size();
+  if (buf && cap >= bytes) memcpy(buf, out.w.data(), bytes);
+  return (int64_t)bytes;
+}
+
+template <class F, class C>
+int test_instance_verify(vimz_ctx* ctx, int curve, const vimz_r1cs* R, const vimz_bases* ck, const uint64_t digest[4], uint32_t side_tag, const char* label,
+                         const uint64_t inst[28], int has_E, const uint64_t* words, size_t n_words) {
+  typedef typename C::Base FS;
+  std::vector<F> sc, dg;
+  std::vector<Affine<FS>> pts;
+  if (!canon_in(inst + 16, 3, sc) || !canon_in(digest, 1, dg)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_instance_verify: element not below the modulus");
+  const int bad = points_in(inst, 2, pts);
+  if (bad == 1) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_instance_verify: coordinate not below the modulus");
+  if (bad == 2) return 0;          // (a commitment off the curve: rejected, as Reader::point rejects one inside a proof)
+  Affine<FS> Ugen;
+  int rc = derive_ipa_u<C>(ctx, curve, &Ugen);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  P_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  TestSide T; TestShape<F> H;
+  if ((rc = test_side_build<F>(ctx, R, ck, T, H))) return rc;
+  Instance<F, FS> I;
+  I.cW = pts[0]; I.cE = pts[1]; I.u = sc[0]; I.X0 = sc[1]; I.X1 = sc[2]; I.has_E = has_E != 0;
+  Transcript tr(label);
+  Reader in{words, n_words};
+  bool ok = false;
+  try { ok = spartan_verify<F, C>(ctx, T.cache, T.S, s, ck, Ugen, dg[0], I, H, side_tag, tr, in); }
+  catch (const std::exception& e) { return vz_fail(ctx, VIMZ_ERR_INVALID, e.what()); }
+  P_TRY(hipStreamSynchronize(s));
+  return ok && in.ok && in.pos == in.n ? 1 : 0;
+}
+
+template <class Fn>
+int64_t instance_dispatch(vimz_ctx* ctx, int curve, size_t n_c, size_t n_w, const vimz_coo* A, const vimz_coo* B, const vimz_coo* C, const vimz_bases* ck, const char* who, Fn fn) {
+  if (curve != VIMZ_CURVE_BN254_G1 && curve != VIMZ_CURVE_GRUMPKIN) return vz_fail(ctx, VIMZ_ERR_INVALID, who);
+  if (n_c < 2 || n_w < 4 || n_c > ((size_t)1 << 21) || n_w > ((size_t)1 << 21) || ck->curve != curve) return vz_fail(ctx, VIMZ_ERR_INVALID, who);
+  size_t big = 1; while (big < std::max(n_c, n_w)) big <<= 1;
+  if (ck->n < big) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_instance: the commitment key is shorter than the padded shape");
+  vimz_r1cs* R = nullptr;
+  const int rc = vimz_r1cs_upload(ctx, curve == VIMZ_CURVE_BN254_G1 ? VIMZ_FIELD_BN254_FR : VIMZ_FIELD_BN254_FQ, n_c, n_w, A, B, C, VIMZ_FORM_CANONICAL, &R);
+  if (rc) return rc;
+  int64_t out;
+  try { out = fn(R); } catch (const std::exception& e) { out = vz_fail(ctx, VIMZ_ERR_INVALID, e.what()); }
+  vimz_r1cs_free(ctx, R);
+  return out;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vimz_test_spartan_eq(vimz_ctx* ctx, int field, const uint64_t* point, size_t k, uint64_t* table_out) {
+  if (!ctx || !point || !table_out || k < 1 || k > 21) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_eq: bad argument");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  P_TRY(hipSetDevice(ctx->device));
+  const int rc = scalar_field_dispatch(field, [&](auto f) { typedef decltype(f) F; return test_eq<F>(ctx, point, k, table_out); });
+  return rc == VIMZ_ERR_INVALID ? vz_fail(ctx, rc, "vimz_test_spartan_eq: bad argument") : rc;
+}
+
+int vimz_test_spartan_sumcheck(vimz_ctx* ctx, int field, int kind, size_t k, const uint64_t* const vecs[5], const uint64_t u[4], const uint64_t* challenges,
+                               uint64_t* msgs_out, uint64_t* finals_out) {
+  if (!ctx || !vecs || !challenges || !msgs_out || !finals_out || k < 1 || k > 21 || kind < 0 || kind > 1) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_sumcheck: bad argument");
+  for (int q = 0; q < (kind == 0 ? 4 : 2); q++) if (!vecs[q]) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_sumcheck: NULL vector");
+  if (kind == 0 && !u) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_sumcheck: the outer check needs u");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  P_TRY(hipSetDevice(ctx->device));
+  const int rc = scalar_field_dispatch(field, [&](auto f) { typedef decltype(f) F; return test_sumcheck<F>(ctx, kind, k, vecs, u, challenges, msgs_out, finals_out); });
+  return rc == VIMZ_ERR_INVALID ? vz_fail(ctx, rc, "vimz_test_spartan_sumcheck: bad argument") : rc;
+}
+
+int vimz_test_spartan_ipa_vec(vimz_ctx* ctx, int field, size_t k, const uint64_t* a, const uint64_t* b, const uint64_t* challenges, uint64_t* dots_out, uint64_t finals_out[8]) {
+  if (!ctx || !a || !b || !challenges || !dots_out || !finals_out || k < 1 || k > 21) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_ipa_vec: bad argument");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  P_TRY(hipSetDevice(ctx->device));
+  const int rc = scalar_field_dispatch(field, [&](auto f) { typedef decltype(f) F; return test_ipa_vec<F>(ctx, k, a, b, challenges, dots_out, finals_out); });
+  return rc == VIMZ_ERR_INVALID ? vz_fail(ctx, rc, "vimz_test_spartan_ipa_vec: bad argument") : rc;
+}
+
+int vimz_test_spartan_fold_bases(vimz_ctx* ctx, int curve, const uint64_t* points_xy, size_t half, const uint64_t x128[2], uint64_t* out_xy) {
+  if (!ctx || !points_xy || !x128 || !out_xy || half < 1 || half > ((size_t)1 << 20) || (curve != VIMZ_CURVE_BN254_G1 && curve != VIMZ_CURVE_GRUMPKIN))
+    return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_fold_bases: bad argument");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  P_TRY(hipSetDevice(ctx->device));
+  return curve == VIMZ_CURVE_BN254_G1 ? test_fold_bases<BnG1>(ctx, points_xy, half, x128, out_xy) : test_fold_bases<Grumpkin>(ctx, points_xy, half, x128, out_xy);
+}
+
+int64_t vimz_test_spartan_instance(vimz_ctx* ctx, int curve, size_t n_c, size_t n_w, const vimz_coo* A, const vimz_coo* B, const vimz_coo* C, const uint64_t* Z,
+                                   const uint64_t* E, const vimz_bases* ck, const uint64_t digest[4], uint32_t side_tag, const char* label, void* buf, size_t cap) {
+  if (!ctx || !A || !B || !C || !Z || !ck || !digest || !label) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_instance: bad argument");
+  return instance_dispatch(ctx, curve, n_c, n_w, A, B, C, ck, "vimz_test_spartan_instance: bad argument", [&](const vimz_r1cs* R) -> int64_t {
+    return curve == VIMZ_CURVE_BN254_G1 ? test_instance<Fe, BnG1>(ctx, curve, R, Z, E, ck, digest, side_tag, label, buf, cap)
+                                        : test_instance<Fq, Grumpkin>(ctx, curve, R, Z, E, ck, digest, side_tag, label, buf, cap);
+  });
+}
+
+int vimz_test_spartan_instance_verify(vimz_ctx* ctx, int curve, size_t n_c, size_t n_w, const vimz_coo* A, const vimz_coo* B, const vimz_coo* C, const vimz_bases* ck,
+                                      const uint64_t digest[4], uint32_t side_tag, const char* label, const uint64_t inst[28], int has_E, const uint64_t* words,
+                                      size_t n_words) {
+  if (!ctx || !A || !B || !C || !ck || !digest || !label || !inst || (!words && n_words)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_instance_verify: bad argument");
+  return (int)instance_dispatch(ctx, curve, n_c, n_w, A, B, C, ck, "vimz_test_spartan_instance_verify: bad argument", [&](const vimz_r1cs* R) -> int64_t {
+    return curve == VIMZ_CURVE_BN254_G1 ? test_instance_verify<Fe, BnG1>(ctx, curve, R, ck, digest, side_tag, label, inst, has_E, words, n_words)
+                                        : test_instance_verify<Fq, Grumpkin>(ctx, curve, R, ck, digest, side_tag, label, inst, has_E, words, n_words);
+  });
+}
+
+}  // extern "C"
+#endif  // VIMZ_TESTING
