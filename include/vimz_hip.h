@@ -603,7 +603,7 @@ int64_t vimz_decider_key_contribute(vimz_ctx* ctx, const void* key_in, size_t le
  * first_bad = {VIMZ_KEYCHAIN_AT_*, index}: the first finding's place — for _ORIGIN_DELTA / _FINAL_DELTA the index is 0 (delta1) or 1 (delta2); for _RECORD the record's
  * number; for _ORIGIN_LH / _FINAL_LH the point's index in l‖h; for _FIXED_PART the offset in 64-bit words of the first difference; {0, 0} when only _LAST or _RATIO fail.
  * A verified chain means: the final key is sound if the origin key is and ANY ONE contributor forgot their delta'.  That the origin key derives from a given
- * string and circuit is not judged here; there is no random beacon.  seconds (optional) = {host conversion and host point checks, per-point flags (upload included),
+ * string and circuit is judged by vimz_decider_key_verify_origin; there is no random beacon.  seconds (optional) = {host conversion and host point checks, per-point flags (upload included),
  * combination, equations}.  VIMZ_ERR_INVALID: a NULL pointer (seconds apart), a key or a record with the wrong magic or length. */
 #define VIMZ_KEYCHAIN_COORD 0x1u          /* a coordinate is not below q */
 #define VIMZ_KEYCHAIN_OFF_CURVE 0x2u      /* a point is not on its curve */
@@ -622,6 +622,51 @@ int64_t vimz_decider_key_contribute(vimz_ctx* ctx, const void* key_in, size_t le
 #define VIMZ_KEYCHAIN_AT_FIXED_PART 6
 int vimz_decider_key_verify_contributions(vimz_ctx* ctx, const void* origin, size_t origin_len, const void* final_key, size_t final_len, const uint64_t* records, size_t n_records,
                                           uint32_t* result, uint64_t first_bad[2], double seconds[4]);
+/* Judges a key someone else hands over (what snarkjs's `zkey verify` checks against an r1cs and a ptau): `key` (vimz_decider_key_save's bytes) is the key
+ * vimz_decider_setup_from_powers would derive from THIS string for THIS prover's decider circuit, for the delta that its delta1/delta2 commit to.  delta is never
+ * known and nothing is derived again: every query is linear in the string's Lagrange basis, so under rho in (128 bits)^m and rho' in (128 bits)^(n-1) from the OS (wiped
+ * on host and device on every path) the combination of a query equals sparse products of the circuit's matrices with rho (on the GPU), inverse NTTs over Fr and MSMs over
+ * the string's own powers — sum rho_i·a_i = MSM(tau_g1, c_A), the same for b1 and, in G2 over tau_g2, for b2; sum over the public wires rho_i·ic_i = K(P) (gamma = 1);
+ * e(sum over the private wires rho_i·l_i, delta2) = e(K(Q), G2); e(sum rho'_j·h_j, delta2) = e(MSM(tau_g1[:2n-1], s), G2) (vimz_amd/csrc/g16_key_origin.hip states c_X, K
+ * and s) — each wrongly accepted with probability at most 2^-128.  The mode, light or full, is read from the blob and the circuit is synthesised for it.  Stage by
+ * stage, a stage only when the ones before it found nothing:  the HEADER's (m, n_pub, n_c, n, len_z, mode) and pp_hash are this prover's decider circuit's, and the
+ * FIXED WORDS are the string's: alpha1 = alpha_g1[0], beta1 = beta_g1[0], beta2 = beta_g2, gamma2 = G2, the KZG point = tau_g2[1];  the POINTS — delta1, delta2 on
+ * their curves, not the identity, delta2 killed by r (host); every coordinate below q, every point of ic, a, b1, l, h on the curve and every non-identity point of b2 on
+ * the twist and killed by r, point by point (GPU; the identity is allowed in the queries: _save writes zeros for wires no matrix touches);  the EQUATIONS, all
+ * evaluated, with e(delta1, G2) = e(G1, delta2).
+ * An accepted key is sound if the string is: it is that set-up's key for SOME delta, whoever knows it — so a key that has had contributions passes too, checked
+ * directly against string and circuit; who contributed is vimz_decider_key_verify_contributions' matter.  NOT judged: the string itself (vimz_powers_verify;
+ * hip.verify_key_origin(verify_powers=True) runs it first) and who knows delta.
+ * Returns VIMZ_OK whenever the key was judged: a bad key is a verdict, not an error.  *result = 0: accepted; otherwise VIMZ_KEYORIGIN_* bits.  first_bad =
+ * {VIMZ_KEYORIGIN_AT_*, index}: for _HEADER the header word (1 m .. 6 mode, 7..10 pp_hash); for _FIXED 0 the KZG point, 1 alpha1, 2 beta1, 3 beta2, 4 gamma2; for _DELTA 0
+ * delta1, 1 delta2; for an array the first flagged point of the first array that has one (*result then holds that array's findings alone); {0, 0} when only
+ * equations fail.  seconds (optional) = {circuit synthesis, host conversion + fixed words, per-point flags (uploads included), circuit side (products, NTTs, MSMs),
+ * key-side combinations + pairings}.  VIMZ_ERR_INVALID with a message: a NULL pointer (seconds apart), a blob with the wrong magic or length, n_pow < n or n_tau_g1 <
+ * 2n - 1 for the key's domain n, an unknown form, a point of the STRING with a coordinate not below q or off its curve (the string's fault, not the key's).  Runs on the
+ * context's stream under the context's lock; one array of the key is on the device at a time (peak device memory: g16_key_origin.hip). */
+#define VIMZ_KEYORIGIN_COORD 0x1u         /* a coordinate is not below q */
+#define VIMZ_KEYORIGIN_OFF_CURVE 0x2u     /* a point is not on its curve */
+#define VIMZ_KEYORIGIN_DELTA 0x4u         /* a delta point is the identity, or delta1 and delta2 are not of one delta */
+#define VIMZ_KEYORIGIN_SUBGROUP 0x8u      /* delta2 or a point of b2 is outside the subgroup of order r */
+#define VIMZ_KEYORIGIN_HEADER 0x10u       /* sizes, mode or pp_hash are not this prover's decider circuit's */
+#define VIMZ_KEYORIGIN_FIXED_POINTS 0x20u /* alpha1, beta1, beta2, gamma2 or the KZG point is not the string's */
+#define VIMZ_KEYORIGIN_A 0x40u            /* the a query is not the string's and circuit's */
+#define VIMZ_KEYORIGIN_B1 0x80u
+#define VIMZ_KEYORIGIN_B2 0x100u
+#define VIMZ_KEYORIGIN_IC 0x200u
+#define VIMZ_KEYORIGIN_L 0x400u           /* ... for the delta of delta2 */
+#define VIMZ_KEYORIGIN_H 0x800u
+#define VIMZ_KEYORIGIN_AT_HEADER 1
+#define VIMZ_KEYORIGIN_AT_FIXED 2
+#define VIMZ_KEYORIGIN_AT_DELTA 3
+#define VIMZ_KEYORIGIN_AT_IC 4
+#define VIMZ_KEYORIGIN_AT_A 5
+#define VIMZ_KEYORIGIN_AT_B1 6
+#define VIMZ_KEYORIGIN_AT_L 7
+#define VIMZ_KEYORIGIN_AT_H 8
+#define VIMZ_KEYORIGIN_AT_B2 9
+int vimz_decider_key_verify_origin(vimz_cf* prover, const void* key, size_t len, const uint64_t* tau_g1, size_t n_tau_g1, const uint64_t* tau_g2, const uint64_t* alpha_g1,
+                                   const uint64_t* beta_g1, size_t n_pow, const uint64_t beta_g2[16], int form, uint32_t* result, uint64_t first_bad[2], double seconds[5]);
 /* Decider::prove for the IVC proof `ivc` holds (same shapes and keys as the decider's prover; left unchanged; at least one step): final fold, KZG
  * openings, Groth16 proof.  words_out: the 25 calldata words (vimz_amd/calldata.py names them), public_out: the info[2] public inputs; canonical,
  * 4 little-endian limbs each.  VIMZ_ERR_UNSAT when the proof does not satisfy the decider's statement (full decider: including a running CycleFold

@@ -125,6 +125,22 @@ int64_t vimz_testing_decider_key_contribute_delta(vimz_ctx* ctx, const void* key
 int vimz_test_ratio_rlc(vimz_ctx* ctx, const uint64_t* before, const uint64_t* after, size_t n, const uint64_t* rho, int form, uint64_t* out /* S, S' */);
 int vimz_test_ratio_rlc_forms(vimz_ctx* ctx, const uint64_t* before, const uint64_t* after, size_t n, const uint64_t* rho, int form, int launches, int reps, uint64_t* out,
                               double* rep_seconds);
+/* The origin check of a key (vimz_amd/csrc/g16_key_origin.hip) on a caller's shapes, through the functions the product calls.  csr = {row_ptr of A, B, C; col of A, B, C;
+ * coef of A, B, C}: a builder's CSRs as they are (row_ptr: n_c + 1 offsets; col: a wire number below m; coef: an index into dict), nnz their entries; dict: n_dict
+ * canonical coefficients below r of 4 words.  An offset, wire number or index out of bounds is VIMZ_ERR_INVALID with a message: nothing is launched.
+ * _spmv_dict: g16_spmv_upload, then ONE g16_spmv3_dict launch (k_spmv3_dict): out_q[i] = (row i of matrix q)·v for i < n_c, zero for n_c <= i < n; v: m canonical
+ * elements of 4 words, out_a, out_b, out_c: n >= n_c canonical elements each.
+ * _key_origin: vimz_decider_key_verify_origin's driver on that R1CS instead of the decider's — m wires, n_pub public inputs, n_c constraints, the domain 2^logn >=
+ * n_c + n_pub + 1, the header's pp_hash words (len_z and mode are not compared: such a circuit has neither) — with a GIVEN rho ‖ rho': m + 2^logn - 1 scalars of 2
+ * words (any 128-bit values).  The product call is this same function with the decider's circuit and the OS's randomness.  points_out (zeros unless the equations
+ * were reached): the key-side sums of a (8 words), b1 (8), b2 (16), ic (8), l (8), h (8), then the string-side a (8), b1 (8), b2 (16), K(P) (8), K(Q) (8) and the h
+ * combination (8) — canonical, the identity as zeros. */
+int vimz_test_g16_spmv_dict(vimz_ctx* ctx, const uint32_t* const csr[9], const size_t nnz[3], const uint64_t* dict, size_t n_dict, size_t m, size_t n_c, size_t n, const uint64_t* v,
+                            uint64_t* out_a, uint64_t* out_b, uint64_t* out_c);
+int vimz_test_key_origin(vimz_ctx* ctx, const uint32_t* const csr[9], const size_t nnz[3], const uint64_t* dict, size_t n_dict, size_t m, size_t n_pub, size_t n_c, int logn,
+                         const uint64_t pp_hash[4], const void* key, size_t len, const uint64_t* tau_g1, size_t n_tau_g1, const uint64_t* tau_g2, const uint64_t* alpha_g1,
+                         const uint64_t* beta_g1, size_t n_pow, const uint64_t beta_g2[16], int form, const uint64_t* rho, uint32_t* result, uint64_t first_bad[2],
+                         uint64_t points_out[112]);
 /* The chains of the full decider's check 5 (vimz_amd/csrc/aug/decider_cf.hpp: every scalar walks the 127 two-bit windows of its generator's table by affine
  * additions from the derived generator H) over a caller's generators and scalars, through the functions the prover calls: where = 0 the host's
  * (cf_open_chains_host; ctx may be NULL), where = 1 the device's (k_cf_open_chains, the scalars uploaded in Montgomery form as the prover holds them, both

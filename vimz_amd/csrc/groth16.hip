@@ -20,6 +20,7 @@
 #include "decider_chains.hpp"
 #include "g16_powers.hpp"
 #include "g16_key_contrib.hpp"
+#include "g16_key_origin.hpp"
 #include "pairing.hpp"
 #include "vecops_api.hpp"
 #ifdef VIMZ_TESTING
@@ -504,8 +505,9 @@ int kzg_vk_matches_srs(vimz_cf* v, const G2PAff& vk, const char* who) {
   return VIMZ_OK;
 }
 
+}  // namespace
 // What every set-up begins with: the KZG verifying key (optional) checked against the prover's SRS, the decider circuit for the prover's shapes, the key's sizes
-// and the constants of the domain
+// and the constants of the domain  (declared in g16_key_origin.hpp: the origin check of a key starts from the same circuit)
 int decider_setup_head(vimz_cf* v, const uint64_t kzg_vk_g2[16], bool light, vimz_decider& d) {
   vimz_ctx* ctx = v->ctx;
   d.vk = v; d.ctx = ctx;
@@ -526,6 +528,7 @@ int decider_setup_head(vimz_cf* v, const uint64_t kzg_vk_g2[16], bool light, vim
   if (!domain_constants(K, K.logn)) return vz_fail(ctx, VIMZ_ERR_INVALID, "decider: root of unity");
   return VIMZ_OK;
 }
+namespace {
 
 int decider_setup_impl(vimz_cf* v, const uint64_t kzg_vk_g2[16], const Trapdoor& td, bool light, vimz_decider** out, double seconds[4]) {
   vimz_ctx* ctx = v->ctx;
@@ -641,7 +644,9 @@ void host_parallel(uint64_t n, const std::function<void(uint64_t, uint64_t)>& f)
 }
 bool string_point_on_curve(const G1Aff& p) { return vz::pairing::g1_on_curve(p); }
 bool string_point_on_curve(const G2PAff& p) { return vz::pairing::g2_on_curve(p); }
+}  // namespace
 // n points of a string as words (form = VIMZ_FORM_*) -> Montgomery coordinates.  0: fine; 1: a coordinate is not below q; 2: a point is not on its curve
+// (declared in g16_key_origin.hpp, instantiated below for both groups)
 template <class A>
 int string_points_in(const uint64_t* words, size_t n, int form, A* out) {
   const size_t per = sizeof(A) / sizeof(Fq);
@@ -659,6 +664,9 @@ int string_points_in(const uint64_t* words, size_t n, int form, A* out) {
   });
   return bad.load();
 }
+template int string_points_in<G1Aff>(const uint64_t*, size_t, int, G1Aff*);
+template int string_points_in<G2PowAff>(const uint64_t*, size_t, int, G2PowAff*);
+namespace {
 
 // delta_given: the test hook's; NULL: drawn from the OS.  seconds (optional) = {synthesis, checks + upload, transforms, column sums, l/h scaling + key tables, total}
 int decider_setup_powers_impl(vimz_cf* v, bool light, const PowersString& S, const Fe* delta_given, vimz_decider** out, double seconds[6]) {
@@ -888,6 +896,46 @@ VerifierKey key_of(const vimz_decider* d) {
 G1Aff g16_g1_generator() { return g1_generator(); }
 G2PowAff g16_g2_generator() { return g2_generator(); }
 bool g16_os_random(void* buf, size_t n) { return os_random(buf, n); }
+
+// what the origin check of a key (g16_key_origin.hip) shares with the set-ups and the prover: the circuit a set-up head leaves, the domain's inverse transform over
+// scalars, the MSM's resident form of a device array of points, and the bit-plane MSM over G2
+vimz_decider* g16_decider_new() { return new vimz_decider(); }
+void g16_decider_delete(vimz_decider* d) { delete d; }
+void g16_decider_circuit(const vimz_decider& d, G16CircuitView* out) {
+  const cb::BuilderT<Fe>& b = d.circ.b;
+  const cb::Csr* Ms[3] = {&b.A, &b.B, &b.C};
+  for (int q = 0; q < 3; q++) { out->row_ptr[q] = Ms[q]->row_ptr.data(); out->n_row_ptr[q] = Ms[q]->row_ptr.size(); out->col[q] = Ms[q]->col.data(); out->coef[q] = Ms[q]->coef.data(); out->nnz[q] = Ms[q]->col.size(); }
+  static_assert(sizeof(Fe) == 32, "a dictionary entry is 8 words");
+  out->dict = (const uint32_t*)b.dict.data(); out->n_dict = b.dict.size();
+  out->m = d.key.m; out->n_pub = d.key.n_pub; out->n_c = d.key.n_c; out->logn = d.key.logn;
+  out->len_z = d.circ.len_z; out->mode = d.circ.full ? 0 : 1; out->whole_header = true;
+  const Fe c = Fe::from_mont(d.vk->c1->digest); memcpy(out->pp_hash, c.v, 32);
+}
+// host_spmv3 over the decider's matrices with a vector of ones, timed: what k_spmv3_dict's time is recorded beside (profiles/key_origin.txt; VIMZ_KEY_ORIGIN_STATS)
+double g16_decider_host_spmv3_seconds(const vimz_decider& d) {
+  const std::vector<Fe> z(d.circ.b.n_wires, Fe::one());
+  std::vector<Fe> out[3];
+  const double t0 = now_s();
+  host_spmv3(d.circ.b, z, out);
+  return now_s() - t0;
+}
+struct G16Domain { G16Key K; };
+int g16_domain_new(vimz_ctx* ctx, hipStream_t s, int logn, G16Domain** out) {
+  std::unique_ptr<G16Domain> D(new G16Domain());
+  if (!domain_constants(D->K, logn)) return vz_fail(ctx, VIMZ_ERR_INVALID, "decider: root of unity");
+  const int rc = domain_tables(ctx, s, D->K);
+  if (rc) { free_key_raw(D->K); return rc; }
+  *out = D.release();
+  return VIMZ_OK;
+}
+void g16_domain_free(G16Domain* D) { if (D) { free_key_raw(D->K); delete D; } }
+void g16_domain_n_inv(const G16Domain* D, uint32_t out[8]) { memcpy(out, D->K.n_inv.v, 32); }
+hipError_t g16_domain_intt_unscaled(hipStream_t s, uint32_t* d, const G16Domain* D) { return ntt(s, d, D->K, true); }
+int g16_bases_from_device(vimz_ctx* ctx, const G1Aff* d_pts, size_t n, vimz_bases** out) { return bases_from_device(ctx, d_pts, n, out); }
+void g16_bases_free_raw(vimz_bases* b) { if (b) { if (b->d) hipFree(b->d); delete b; } }
+int g16_g2_msm(vimz_ctx* ctx, hipStream_t s, const G2PowAff* bases, const uint32_t* wires, const uint32_t* idx, uint32_t n, uint32_t* canon, XYZZ<vz::pairing::Fq2>* out) {
+  return g2_msm(ctx, s, bases, wires, idx, n, canon, out);
+}
 
 extern "C" {
 

@@ -1047,6 +1047,53 @@ def keychain_problems(bits):
     return [name for bit, name in KEYCHAIN_BITS.items() if bits & bit]
 
 
+KEYORIGIN_BITS = {0x1: "a coordinate is not below q", 0x2: "a point is not on its curve", 0x4: "a delta point is the identity, or delta1 and delta2 are not of one delta",
+                  0x8: "delta2 or a point of b2 is outside the subgroup", 0x10: "the header (sizes, mode, pp_hash) is not this prover's decider circuit's",
+                  0x20: "alpha1, beta1, beta2, gamma2 or the KZG point is not the string's", 0x40: "the a query is not the string's and circuit's",
+                  0x80: "the b1 query is not the string's and circuit's", 0x100: "the b2 query is not the string's and circuit's", 0x200: "the ic points are not the string's and circuit's",
+                  0x400: "the l query is not the string's and circuit's over delta2", 0x800: "the h query is not the string's over delta2"}      # VIMZ_KEYORIGIN_*
+KEYORIGIN_BIT_NAMES = ("COORD", "OFF_CURVE", "DELTA", "SUBGROUP", "HEADER", "FIXED_POINTS", "A", "B1", "B2", "IC", "L", "H")
+KEYORIGIN_PLACES = (None, "header word", "fixed word (0 KZG, 1 alpha1, 2 beta1, 3 beta2, 4 gamma2)", "delta point", "ic point", "a point", "b1 point", "l point", "h point",
+                    "b2 point")      # first_bad[0]: VIMZ_KEYORIGIN_AT_*
+
+
+def verify_key_origin(prover, powers, blob, verify_powers=False, seconds=None):
+    """vimz_decider_key_verify_origin: is `blob` (Decider.save_key's bytes, from anyone) the key a set-up from `powers` (iden3.read_ptau's dictionary) derives for
+    `prover`'s decider circuit — light or full as the blob says —, for the delta its delta points commit to?  What snarkjs's `zkey verify` checks against an r1cs and a
+    ptau; delta is never known and nothing is derived again (random combinations under 128-bit scalars from the OS: sparse products of the circuit's matrices, inverse
+    NTTs and MSMs over the string on the GPU, three products of pairings).  Returns (result, first_bad): result 0 = accepted, otherwise a union of KEYORIGIN_BITS;
+    first_bad = (place — KEYORIGIN_PLACES names it —, index), (0, 0) when only equations fail.  A key that has had contributions passes too; who contributed is
+    verify_key_contributions' matter.  The string is taken as given unless verify_powers is true: the prefix the key's domain reads then goes through hip.verify_powers
+    first and a refused string raises VimzError(ERR_INVALID) before any key work.  seconds: a list that receives [circuit synthesis, host conversion + fixed words,
+    per-point flags, circuit side, key-side combinations + pairings].  VimzError(ERR_INVALID): not a key, a string shorter than the key's domain needs, a bad point of
+    the string."""
+    b = np.ascontiguousarray(np.frombuffer(bytes(blob), dtype=np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else blob, dtype=np.uint8).reshape(-1)
+    ctx = prover.ctx
+    a = {name: np.ascontiguousarray(powers[name], dtype=np.uint64).reshape(-1, 8 * group) for name, group in _LAGRANGE_ARRAYS + (("beta_g2", 2),)}
+    n_pow = min(a["tau_g2"].shape[0], a["alpha_g1"].shape[0], a["beta_g1"].shape[0])
+    if a["beta_g2"].shape[0] < 1:
+        raise L.VimzError(L.ERR_INVALID, "verify_key_origin: the string has no beta_g2")
+    if verify_powers:
+        n = int.from_bytes(b[32:40].tobytes(), "little") if b.size >= 40 else 0      # the domain the key's header names
+        if n < 2 or n > n_pow or 2 * n - 1 > a["tau_g1"].shape[0]:
+            raise L.VimzError(L.ERR_INVALID, f"verify_key_origin: the key's domain is {n}, the string holds {n_pow} powers ({a['tau_g1'].shape[0]} of tau in G1)")
+        require_good_powers(ctx, powers, n, "verify_key_origin")
+    vp = C.c_void_p
+    result, first, sec = C.c_uint32(0), np.zeros(2, dtype=np.uint64), (C.c_double * 5)()
+    fn = ctx.lib.vimz_decider_key_verify_origin
+    fn.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp, C.c_size_t, vp, C.c_int, C.POINTER(C.c_uint32), vp, C.POINTER(C.c_double)]
+    ctx._chk(fn(prover.h, _ptr(b), b.size, _ptr(a["tau_g1"]), a["tau_g1"].shape[0], _ptr(a["tau_g2"]), _ptr(a["alpha_g1"]), _ptr(a["beta_g1"]), n_pow, _ptr(a["beta_g2"]), L.FORM_MONTGOMERY,
+                 C.byref(result), _ptr(first), sec))
+    if seconds is not None:
+        seconds[:] = list(sec)
+    return int(result.value), (int(first[0]), int(first[1]))
+
+
+def keyorigin_problems(bits):
+    """the names of an origin verdict's bits"""
+    return [name for bit, name in KEYORIGIN_BITS.items() if bits & bit]
+
+
 def set_head_rows(rows):
     """vimz_set_head_rows: rows of a short fold call whose Poseidon chains run on the host (0: all on the GPU; -1: the library's policy)."""
     lib = L.lib()

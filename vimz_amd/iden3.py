@@ -236,18 +236,56 @@ def _verify_contributions(argv):
     return 1
 
 
+def _verify_key(argv):
+    """verify-key FILE.ptau TRANSFORMATION RESOLUTION KEY [--verify]: judges on GPU 0 that KEY (vimz_decider_key_save's bytes, from anyone) is the key a set-up from the
+    string derives for that step circuit's decider — light or full as the key says —, for the delta its delta points commit to (hip.verify_key_origin); prints the
+    verdict's bit names and the times; exit status 0 accepted, 1 refused.  --verify: the string's prefixes are judged first (hip.verify_powers)."""
+    verify = "--verify" in argv
+    args = [a for a in argv if a != "--verify"]
+    if len(args) != 5 or any(a.startswith("--") for a in args):
+        print(USAGE, file=sys.stderr)
+        return 2
+    from . import folding, hip
+    with open(args[1], "rb") as fp:
+        powers = read_ptau(fp.read())
+    blob = np.fromfile(args[4], dtype=np.uint8)
+    sec = [0.0] * 5
+    ctx = hip.Context(0)
+    try:
+        circuit, params = folding.prepare_folding(ctx, args[2], args[3], window_tables=0, backend="sonobe", powers=powers, verify_powers=verify)
+        cf = hip.CycleFoldIVC(ctx, circuit, params.ck, params.secondary_key(), max_batch=1)
+        try:
+            bits, first = hip.verify_key_origin(cf, powers, blob, verify_powers=verify, seconds=sec)
+        finally:
+            cf.close(); params.free()
+    finally:
+        ctx.close()
+    what = f"{args[4]} against {args[1]} and the decider of {args[2]} {args[3]}"
+    times = f"synthesis {sec[0]:.3f} s, host conversion {sec[1]:.3f} s, per-point flags {sec[2]:.3f} s, circuit side {sec[3]:.3f} s, combinations and pairings {sec[4]:.3f} s"
+    if not bits:
+        print(f"verify-key: {what}: accepted ({times})")
+        return 0
+    names = " ".join(n for k, n in enumerate(hip.KEYORIGIN_BIT_NAMES) if bits >> k & 1)
+    at = f"; first: {hip.KEYORIGIN_PLACES[first[0]]} {first[1]}" if first[0] else ""
+    print(f"verify-key: {what}: REFUSED (0x{bits:x}: {names}): " + "; ".join(hip.keyorigin_problems(bits)) + f"{at} ({times})")
+    return 1
+
+
 USAGE = ("usage: python -m vimz_amd.iden3 lagrange FILE.ptau LOGN OUT.npz\n"
          "       python -m vimz_amd.iden3 decider-key FILE.ptau TRANSFORMATION RESOLUTION OUT.key [--light] [--verify]\n"
          "       python -m vimz_amd.iden3 verify FILE.ptau [POINTS]\n"
          "       python -m vimz_amd.iden3 contribute IN.key OUT.key RECORDS\n"
-         "       python -m vimz_amd.iden3 verify-contributions ORIGIN.key FINAL.key RECORDS")
+         "       python -m vimz_amd.iden3 verify-contributions ORIGIN.key FINAL.key RECORDS\n"
+         "       python -m vimz_amd.iden3 verify-key FILE.ptau TRANSFORMATION RESOLUTION KEY [--verify]")
 
 
 def _main(argv):
     """python -m vimz_amd.iden3 lagrange FILE.ptau LOGN OUT.npz: the string's Lagrange bases over the domain of 2^LOGN points (hip.lagrange_from_powers, on GPU 0)
     as an .npz of tau_g1, alpha_g1, beta_g1 (n, 8) and tau_g2 (n, 16) in the file's Montgomery form, with logn.
     python -m vimz_amd.iden3 decider-key ...: _decider_key.  python -m vimz_amd.iden3 verify ...: _verify.
-    python -m vimz_amd.iden3 contribute ... / verify-contributions ...: _contribute, _verify_contributions."""
+    python -m vimz_amd.iden3 contribute ... / verify-contributions ... / verify-key ...: _contribute, _verify_contributions, _verify_key."""
+    if argv and argv[0] == "verify-key":
+        return _verify_key(argv)
     if argv and argv[0] == "decider-key":
         return _decider_key(argv)
     if argv and argv[0] == "verify":
