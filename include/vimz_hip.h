@@ -545,6 +545,55 @@ int vimz_powers_lagrange(vimz_ctx* ctx, int group /* 1: G1, 8 words a point; 2: 
 #define VIMZ_POWERS_BETA 0x400u          /* beta_g1[0] and beta_g2 are not of one beta */
 int vimz_powers_verify(vimz_ctx* ctx, const uint64_t* tau_g1, size_t n_tau_g1, const uint64_t* tau_g2, const uint64_t* alpha_g1, const uint64_t* beta_g1, size_t n_pow,
                        const uint64_t beta_g2[16], int form, uint32_t* result, uint64_t first_bad[2], double seconds[4]);
+/* A contribution to a powers-of-tau string (phase 1 of a ceremony; what snarkjs calls `powersoftau contribute`), on the arrays vimz_powers_verify takes (same layout and
+ * form): tau', alpha', beta' != 0 and three nonces come from the OS and are wiped on every path, host and device; tau_g1[k] and tau_g2[k] become tau'^k times themselves,
+ * alpha_g1[k] alpha'·tau'^k times, beta_g1[k] beta'·tau'^k times — one scalar multiplication a point with a DIFFERENT scalar at every point, on the GPU: ONE vector of
+ * the n_tau_g1 powers of tau' is made on the device, each array goes there alone, is scaled and comes back, and the vector is overwritten before it is freed (peak device
+ * memory: one array and 32 bytes a point of tau_g1) — and beta_g2 becomes beta'·beta_g2 on the host.  The string of (tau, alpha, beta) leaves as the string of
+ * (tau·tau', alpha·alpha', beta·beta').  The *_out arrays have the inputs' sizes and form and may be the inputs; nothing is written unless everything succeeded.
+ * record_out: VIMZ_POWCHAIN_RECORD_WORDS little-endian words — this project's own format (vimz_amd/csrc/g16_powers_contrib.hpp), NOT snarkjs's transcript: magic
+ * "VPOTCTR1", then as canonical words tau_g1[1], alpha_g1[0], beta_g1[0] AFTER the contribution (8 each), T_tau, T_alpha, T_beta (8 each), z_tau, z_alpha, z_beta (4
+ * each): three Schnorr proofs of knowledge of tau', alpha', beta' over the same points BEFORE the contribution, each bound to all six points.  Records are kept apart from
+ * the string, one after another.  The walk over a secret scalar's bits is NOT constant-time, on host or device.  seconds (optional) = {host (conversion, checks, the
+ * record, beta_g2), device (power vector, uploads, scaling, downloads), total}.  VIMZ_ERR_INVALID with a message: a NULL pointer (seconds apart), n_pow < 2, n_tau_g1 <
+ * n_pow, an unknown form, a coordinate not below q, a point off its curve, tau_g1[1], alpha_g1[0] or beta_g1[0] the identity.  The string is otherwise NOT judged —
+ * subgroup membership in G2, that it is a string at all: vimz_powers_verify's matter. */
+#define VIMZ_POWCHAIN_RECORD_WORDS 61
+int vimz_powers_contribute(vimz_ctx* ctx, const uint64_t* tau_g1, size_t n_tau_g1, const uint64_t* tau_g2, const uint64_t* alpha_g1, const uint64_t* beta_g1, size_t n_pow,
+                           const uint64_t beta_g2[16], int form, uint64_t* tau_g1_out, uint64_t* tau_g2_out, uint64_t* alpha_g1_out, uint64_t* beta_g1_out, uint64_t beta_g2_out[16],
+                           uint64_t record_out[VIMZ_POWCHAIN_RECORD_WORDS], double seconds[3]);
+/* Judges a chain of such contributions: the final string (arrays as above) is what n_records contributions (`records`, 61 words each, in order; n_records may be 0) made
+ * of a string whose tau_g1[1], alpha_g1[0], beta_g1[0] were origin_points (24 canonical words; for a new string three times the generator).  Returns VIMZ_OK whenever
+ * the chain was judged: a bad chain is a verdict, not an error.  *result = 0: accepted; otherwise VIMZ_POWCHAIN_* bits.  Stage by stage, a stage only when the ones
+ * before it found nothing:  the POINTS — the origin's three and every record's nine points have coordinates below q, are on the curve and not the identity (the bits
+ * of the first place that has a finding);  KNOWLEDGE, all evaluated — z_s·B_s = T_s + c_s·A_s for the three secrets of every record, B the points of the record
+ * before it (of the origin for the first), and the last record's points (the origin's, without records) are the final string's tau_g1[1], alpha_g1[0], beta_g1[0];
+ * the STRING — the final string goes through vimz_powers_verify as it stands; a refusal sets _STRING, *string_result holds that call's VIMZ_POWERS_* bits (0 otherwise).
+ * first_bad = {VIMZ_POWCHAIN_AT_*, index}: _AT_ORIGIN with the point's number (0 tau, 1 alpha, 2 beta), _AT_RECORD with the first bad record's number,
+ * _AT_STRING_<array> with vimz_powers_verify's index; {0, 0} when only _LAST fails or the string fails by its equations alone.
+ * An accepted chain means: the final string is the powers of ONE tau with consistent alpha and beta, and tau, alpha, beta are unknown to everyone if ANY ONE contributor
+ * forgot their secrets, whatever the origin was — every record holder knew the factor between its points and the ones before, and the string's own check ties every
+ * other point to those three.  It does NOT give: a random beacon (the last contributor can still try secrets until the result suits them), nor compatibility with
+ * snarkjs's transcript, challenge files or response files.  seconds (optional) = {points, knowledge, the string's verdict}.  VIMZ_ERR_INVALID: a NULL pointer
+ * (seconds apart; records when n_records is 0), a record with the wrong magic, and what vimz_powers_verify answers it to. */
+#define VIMZ_POWCHAIN_COORD 0x1u            /* a coordinate is not below q */
+#define VIMZ_POWCHAIN_OFF_CURVE 0x2u        /* a point is not on its curve */
+#define VIMZ_POWCHAIN_IDENTITY 0x4u         /* a point is the identity */
+#define VIMZ_POWCHAIN_KNOWLEDGE_TAU 0x8u    /* a record's proof of knowledge of tau' fails over the points before it */
+#define VIMZ_POWCHAIN_KNOWLEDGE_ALPHA 0x10u
+#define VIMZ_POWCHAIN_KNOWLEDGE_BETA 0x20u
+#define VIMZ_POWCHAIN_LAST 0x40u            /* the last record's points are not the final string's tau_g1[1], alpha_g1[0], beta_g1[0] */
+#define VIMZ_POWCHAIN_STRING 0x80u          /* vimz_powers_verify refuses the final string: its bits are in *string_result */
+#define VIMZ_POWCHAIN_AT_ORIGIN 1
+#define VIMZ_POWCHAIN_AT_RECORD 2
+#define VIMZ_POWCHAIN_AT_STRING_TAU_G1 3    /* 2 + vimz_powers_verify's array number */
+#define VIMZ_POWCHAIN_AT_STRING_TAU_G2 4
+#define VIMZ_POWCHAIN_AT_STRING_ALPHA_G1 5
+#define VIMZ_POWCHAIN_AT_STRING_BETA_G1 6
+#define VIMZ_POWCHAIN_AT_STRING_BETA_G2 7
+int vimz_powers_verify_contributions(vimz_ctx* ctx, const uint64_t origin_points[24], const uint64_t* tau_g1, size_t n_tau_g1, const uint64_t* tau_g2, const uint64_t* alpha_g1,
+                                     const uint64_t* beta_g1, size_t n_pow, const uint64_t beta_g2[16], int form, const uint64_t* records, size_t n_records, uint32_t* result,
+                                     uint32_t* string_result, uint64_t first_bad[2], double seconds[3]);
 /* Decider::preprocess.  prover: supplies shapes, keys and context (must outlive the object).  kzg_vk_g2 (optional): [tau]G2 of the SRS the prover's
  * ck_main is made of (needed by vimz_decider_verify; part of vimz_decider_vk; checked against that SRS: e(srs[1], G2) = e(G1, [tau]G2)).
  * light: 0 = the full decider (the reference's default), non-zero = the `light-test` variant.  The full decider bakes the first generators of the

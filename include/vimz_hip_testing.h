@@ -125,6 +125,19 @@ int64_t vimz_testing_decider_key_contribute_delta(vimz_ctx* ctx, const void* key
 int vimz_test_ratio_rlc(vimz_ctx* ctx, const uint64_t* before, const uint64_t* after, size_t n, const uint64_t* rho, int form, uint64_t* out /* S, S' */);
 int vimz_test_ratio_rlc_forms(vimz_ctx* ctx, const uint64_t* before, const uint64_t* after, size_t n, const uint64_t* rho, int form, int launches, int reps, uint64_t* out,
                               double* rep_seconds);
+/* vimz_powers_contribute (vimz_amd/csrc/g16_powers_contrib.hip) with GIVEN secrets tau', alpha', beta' and nonces k_tau, k_alpha, k_beta — 4 canonical words each, below
+ * r, the secrets non-zero — so that a test compares the string and the record word for word.  Whoever knows the secrets can undo the contribution. */
+int vimz_testing_powers_contribute_secrets(vimz_ctx* ctx, const uint64_t* tau_g1, size_t n_tau_g1, const uint64_t* tau_g2, const uint64_t* alpha_g1, const uint64_t* beta_g1,
+                                           size_t n_pow, const uint64_t beta_g2[16], int form, uint64_t* tau_g1_out, uint64_t* tau_g2_out, uint64_t* alpha_g1_out,
+                                           uint64_t* beta_g1_out, uint64_t beta_g2_out[16], uint64_t record_out[61], const uint64_t secrets[12], const uint64_t nonces[12],
+                                           double seconds[3]);
+/* The two kernels of that contribution on a caller's shapes, through the functions the product queues.
+ * _power_vec: out[i] = w^i for i < count, 1 <= count <= 2^26 (k_power_vec over bitlen(count − 1) bits); w: 4 canonical words below r; out: 4 canonical words each.
+ * _scale_points_by: out[i] = (c·w^i)·P_i for n >= 1 points (k_power_vec, then k_scale_points_by with c as its argument); group = 1: points of G1, 8 words each; 2: of
+ * G2, 16 words (x.c0, x.c1, y.c0, y.c1); form = VIMZ_FORM_* of the coordinates, out in the same form and possibly `points`; the identity as zeros; w, c: 4 canonical
+ * words below r, zero allowed (the production entry never passes one); every input below q and on its curve. */
+int vimz_test_power_vec(vimz_ctx* ctx, const uint64_t w[4], size_t count, uint64_t* out);
+int vimz_test_scale_points_by(vimz_ctx* ctx, int group, const uint64_t* points, size_t n, const uint64_t w[4], const uint64_t c[4], int form, uint64_t* out);
 /* The origin check of a key (vimz_amd/csrc/g16_key_origin.hip) on a caller's shapes, through the functions the product calls.  csr = {row_ptr of A, B, C; col of A, B, C;
  * coef of A, B, C}: a builder's CSRs as they are (row_ptr: n_c + 1 offsets; col: a wire number below m; coef: an index into dict), nnz their entries; dict: n_dict
  * canonical coefficients below r of 4 words.  An offset, wire number or index out of bounds is VIMZ_ERR_INVALID with a message: nothing is launched.

@@ -180,4 +180,31 @@ inline bool ratio_sum_plan(size_t n_chunks, ColsumPlan* plan) {
   return colsum_plan(nullptr, 0, units.data(), units.size(), nullptr, 0, BnFr::MOD.w, 2u, (uint32_t)(2 * n_chunks), plan, nullptr);
 }
 
+// ---- a contribution to a powers-of-tau string (g16_powers_contrib.hip: k_power_vec, k_scale_points_by): what ONE thread does, looped on the CPU by tests/native/powers_contrib_check.cpp ----
+
+// entry `index` of the power vector, w^index as 8 MONTGOMERY words (pt_scale_by multiplies it by c before it walks it), for index < count <= 2^bits; w in Montgomery
+// form.  Square and multiply over exactly `bits` bits, as pt_twiddle: the trip count comes from the host (bitlen(count − 1), 0 for count = 1).
+VZ_HD void pt_power(size_t index, int bits, const Fp<BnFr>& w, uint32_t* out) {
+  typedef Fp<BnFr> Fr;
+  Fr acc = Fr::one();
+  for (int b = bits - 1; b >= 0; b--) {
+    acc = Fr::sqr(acc);
+    if ((index >> b) & 1u) acc = Fr::mul(acc, w);
+  }
+  for (int i = 0; i < 8; i++) out[8 * index + i] = acc.v[i];
+}
+
+// out[index] = (c·pw[index])·in[index]: the scalar is ONE product in Fr (c and pw in Montgomery form) brought to canonical words, then pt_scalar_mul's walk and one
+// inversion.  out may be in: the point is read before it is written and the thread touches its own slot alone.  The identity stays the identity (add_mixed skips
+// it), and a zero scalar gives it.
+template <class F>
+VZ_HD void pt_scale_by(size_t index, const Affine<F>* in, const uint32_t* pw, const Fp<BnFr>& c, Affine<F>* out) {
+  typedef Fp<BnFr> Fr;
+  Fr s;
+  for (int i = 0; i < 8; i++) s.v[i] = pw[8 * index + i];
+  s = Fr::from_mont(Fr::mul(c, s));
+  const Affine<F> p = in[index];
+  out[index] = to_affine(pt_scalar_mul(p, s.v));
+}
+
 }  // namespace vz

@@ -83,3 +83,13 @@ hipError_t g16_powers_rlc_pass(hipStream_t s, const G1Aff* points, size_t n_pair
 // pt_ratio_chunk) —, then g16_column_sums over `sum`, the plan of TWO columns of ratio_sum_plan uploaded for G1.  chunks: 2·g16_powers_rlc_chunks(n) points.  out: as
 // g16_column_sums leaves it (reduced Montgomery coordinates, the identity as zeros).
 hipError_t g16_ratio_rlc(hipStream_t s, const G1Aff* before, const G1Aff* after, size_t n, const uint32_t* rho, const ColsumDevice& sum, G1Aff* chunks, G1Aff* out);
+
+// ---- a contribution to a powers-of-tau string (g16_powers_contrib.hip: vimz_powers_contribute) ------------------------------------------------------------------
+// Queues on `s`: pw[8i ..] = w^i for i < count as 8 Montgomery words (k_power_vec, one thread per power, g16_point_stage.hpp: pt_power over bitlen(count − 1) bits).
+// w: Montgomery, a kernel argument.  When w is a secret so is the vector: the caller overwrites it before freeing it.  count <= 2^31.
+hipError_t g16_power_vec(hipStream_t s, uint32_t* pw, size_t count, const Fe& w);
+// Queues on `s`: out[i] = (c·pw[i])·in[i] for n affine points (device, Montgomery coordinates, the identity as zeros) and the power vector above (n entries or more):
+// k_scale_points_by, one thread per point (pt_scale_by), a DIFFERENT scalar at every point.  c: Montgomery, a kernel argument.  out may be in; output coordinates are
+// canonical.
+hipError_t g16_scale_points_by(hipStream_t s, const G1Aff* in, size_t n, const uint32_t* pw, const Fe& c, G1Aff* out);
+hipError_t g16_scale_points_by(hipStream_t s, const G2PowAff* in, size_t n, const uint32_t* pw, const Fe& c, G2PowAff* out);

@@ -945,6 +945,105 @@ def kzg_from_powers(ctx, powers, n, verify_powers=False):
 
 _LAGRANGE_ARRAYS = (("tau_g1", 1), ("alpha_g1", 1), ("beta_g1", 1), ("tau_g2", 2))      # name, group
 
+POWCHAIN_BITS = {0x1: "a coordinate is not below q", 0x2: "a point is not on its curve", 0x4: "a point is the identity", 0x8: "a record's proof of knowledge of tau' fails",
+                 0x10: "a record's proof of knowledge of alpha' fails", 0x20: "a record's proof of knowledge of beta' fails",
+                 0x40: "the last record's points are not the final string's", 0x80: "the final string is refused"}      # VIMZ_POWCHAIN_*
+POWCHAIN_BIT_NAMES = ("COORD", "OFF_CURVE", "IDENTITY", "KNOWLEDGE_TAU", "KNOWLEDGE_ALPHA", "KNOWLEDGE_BETA", "LAST", "STRING")
+POWCHAIN_PLACES = (None, "the origin's point", "record", "the final string's tau_g1 point", "the final string's tau_g2 point", "the final string's alpha_g1 point",
+                   "the final string's beta_g1 point", "the final string's beta_g2 point")      # first_bad[0]: VIMZ_POWCHAIN_AT_*
+POWCHAIN_RECORD_BYTES = 488
+_POWERS_ARRAYS = _LAGRANGE_ARRAYS + (("beta_g2", 2),)
+
+
+def _powers_args(powers, who):
+    """the five arrays of a string as contiguous uint64 rows, and (n_tau_g1, n_pow)"""
+    a = {name: np.ascontiguousarray(powers[name], dtype=np.uint64).reshape(-1, 8 * group) for name, group in _POWERS_ARRAYS}
+    n_pow = a["tau_g2"].shape[0]
+    if n_pow < 2 or a["alpha_g1"].shape[0] != n_pow or a["beta_g1"].shape[0] != n_pow or a["tau_g1"].shape[0] < n_pow or a["beta_g2"].shape[0] != 1:
+        raise L.VimzError(L.ERR_INVALID, f"{who}: a string holds n >= 2 points each of tau_g2, alpha_g1 and beta_g1, n or more of tau_g1 and one of beta_g2")
+    return a, a["tau_g1"].shape[0], n_pow
+
+
+def contribute_powers(ctx, powers, secrets=None, nonces=None, seconds=None):
+    """vimz_powers_contribute: one contribution to a powers-of-tau string (iden3.read_ptau's dictionary, the file's Montgomery form; what snarkjs's `powersoftau
+    contribute` does) — tau', alpha', beta' drawn from the OS and forgotten, every point multiplied by its own scalar on the GPU: the string of (tau, alpha, beta)
+    becomes the string of (tau·tau', alpha·alpha', beta·beta').  Returns (powers, record): a dictionary in read_ptau's form (iden3.write_ptau takes it) and the
+    record's POWCHAIN_RECORD_BYTES bytes (this project's own format: include/vimz_hip.h) — keep the records of a chain one after another, verify_powers_contributions
+    takes them.  secrets and nonces (three ints each, both or neither) select the TEST hook of libvimz_hip_testing.so.  seconds: a list that receives [host, device,
+    total].  VimzError(ERR_INVALID): a coordinate not below q, a point off its curve, tau_g1[1], alpha_g1[0] or beta_g1[0] the identity."""
+    a, n_g1, n_pow = _powers_args(powers, "contribute_powers")
+    out = {name: np.zeros_like(arr) for name, arr in a.items()}
+    rec, sec = np.zeros(61, dtype=np.uint64), (C.c_double * 3)()
+    vp = C.c_void_p
+    if (secrets is None) != (nonces is None):
+        raise L.VimzError(L.ERR_INVALID, "contribute_powers: secrets= and nonces= go together")
+    argtypes = [vp, vp, C.c_size_t, vp, vp, vp, C.c_size_t, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    if secrets is None:
+        fn, extra = ctx.lib.vimz_powers_contribute, ()
+    else:
+        fn = _seeded(ctx, "vimz_testing_powers_contribute_secrets")
+        words = [np.frombuffer(b"".join(int(x).to_bytes(32, "little") for x in three), dtype="<u8").astype(np.uint64) for three in (secrets, nonces)]
+        if words[0].size != 12 or words[1].size != 12:
+            raise L.VimzError(L.ERR_INVALID, "contribute_powers: three secrets and three nonces")
+        extra, argtypes = (_ptr(words[0]), _ptr(words[1])), argtypes + [vp, vp]
+    fn.argtypes = argtypes + [C.POINTER(C.c_double)]
+    ctx._chk(fn(ctx.h, _ptr(a["tau_g1"]), n_g1, _ptr(a["tau_g2"]), _ptr(a["alpha_g1"]), _ptr(a["beta_g1"]), n_pow, _ptr(a["beta_g2"]), L.FORM_MONTGOMERY,
+                _ptr(out["tau_g1"]), _ptr(out["tau_g2"]), _ptr(out["alpha_g1"]), _ptr(out["beta_g1"]), _ptr(out["beta_g2"]), _ptr(rec), *extra, sec))
+    if seconds is not None:
+        seconds[:] = list(sec)
+    for key in ("power", "ceremony_power"):
+        if key in powers:
+            out[key] = int(powers[key])
+    return out, rec.tobytes()
+
+
+def powers_origin_points(origin):
+    """the 24 canonical words vimz_powers_verify_contributions takes for a chain's origin: from a string (read_ptau's dictionary: its tau_g1[1], alpha_g1[0],
+    beta_g1[0] out of the Montgomery form), from three (x, y) pairs of ints, or 24 words as they are"""
+    if isinstance(origin, dict):
+        rows = [np.ascontiguousarray(origin["tau_g1"], dtype=np.uint64).reshape(-1, 8)[1], np.ascontiguousarray(origin["alpha_g1"], dtype=np.uint64).reshape(-1, 8)[0],
+                np.ascontiguousarray(origin["beta_g1"], dtype=np.uint64).reshape(-1, 8)[0]]
+        raw, minv = b"".join(r.astype("<u8").tobytes() for r in rows), pow(1 << 256, -1, _BN254_Q)
+        coords = [int.from_bytes(raw[i:i + 32], "little") for i in range(0, 192, 32)]
+        if max(coords) >= _BN254_Q:
+            raise L.VimzError(L.ERR_INVALID, "verify_powers_contributions: a coordinate of the origin's points is not below q")
+        coords = [c * minv % _BN254_Q for c in coords]
+    elif isinstance(origin, np.ndarray):
+        return np.ascontiguousarray(origin, dtype=np.uint64).reshape(24)
+    else:
+        coords = [int(c) for p in origin for c in p]
+        if len(coords) != 6 or min(coords) < 0 or max(coords) >= 1 << 256:
+            raise L.VimzError(L.ERR_INVALID, "verify_powers_contributions: the origin is a string, 24 words or three (x, y) points")
+    return np.frombuffer(b"".join(c.to_bytes(32, "little") for c in coords), dtype="<u8").astype(np.uint64)
+
+
+def verify_powers_contributions(ctx, origin, final, records, seconds=None):
+    """vimz_powers_verify_contributions: is `final` (a string in read_ptau's form) what the contributions of `records` (bytes, POWCHAIN_RECORD_BYTES each, in order;
+    may be empty) made of `origin` — a string, or its three points tau_g1[1], alpha_g1[0], beta_g1[0] (powers_origin_points)?  Returns (bits, string_bits, first_bad):
+    bits 0 = accepted, otherwise a union of POWCHAIN_BITS; string_bits: verify_powers' verdict on the final string when that is what refuses (POWERS_PROBLEMS);
+    first_bad = (place — POWCHAIN_PLACES names it —, index).  An accepted chain means the final string is the powers of one tau with consistent alpha and beta that
+    nobody knows if any ONE contributor forgot their secrets, whatever the origin was; there is no random beacon and no compatibility with snarkjs's transcript.
+    seconds: a list that receives [points, knowledge, the string's verdict]."""
+    a, n_g1, n_pow = _powers_args(final, "verify_powers_contributions")
+    o = powers_origin_points(origin)
+    r = np.ascontiguousarray(np.frombuffer(bytes(records), dtype=np.uint8) if isinstance(records, (bytes, bytearray, memoryview)) else records, dtype=np.uint8).reshape(-1)
+    if r.size % POWCHAIN_RECORD_BYTES:
+        raise L.VimzError(L.ERR_INVALID, f"verify_powers_contributions: records are {POWCHAIN_RECORD_BYTES} bytes each, not {r.size} in all")
+    vp = C.c_void_p
+    result, sresult, first, sec = C.c_uint32(0), C.c_uint32(0), np.zeros(2, dtype=np.uint64), (C.c_double * 3)()
+    fn = ctx.lib.vimz_powers_verify_contributions
+    fn.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, C.c_size_t, vp, C.c_int, vp, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp, C.POINTER(C.c_double)]
+    ctx._chk(fn(ctx.h, _ptr(o), _ptr(a["tau_g1"]), n_g1, _ptr(a["tau_g2"]), _ptr(a["alpha_g1"]), _ptr(a["beta_g1"]), n_pow, _ptr(a["beta_g2"]), L.FORM_MONTGOMERY,
+                _ptr(r) if r.size else None, r.size // POWCHAIN_RECORD_BYTES, C.byref(result), C.byref(sresult), _ptr(first), sec))
+    if seconds is not None:
+        seconds[:] = list(sec)
+    return int(result.value), int(sresult.value), (int(first[0]), int(first[1]))
+
+
+def powchain_problems(bits):
+    """the names of a powers chain verdict's bits"""
+    return [name for bit, name in POWCHAIN_BITS.items() if bits & bit]
+
 
 def powers_lagrange(ctx, group, points, logn, form=L.FORM_CANONICAL, seconds=None):
     """vimz_powers_lagrange: the first 2^logn of `points` (rows of 8 words for group 1 = G1, of 16 for group 2 = G2) -> the points [L_j] in the same form, the

@@ -109,6 +109,44 @@ def read_ptau(data):
     return out
 
 
+def write_ptau(powers):
+    """read_ptau's dictionary -> the bytes of a `.ptau` container: the exact inverse of read_ptau (read_ptau(write_ptau(p)) holds p's words).  Writes version 1 and the
+    sections 1–6 in their order and nothing else — no contribution section 7 and none of the Lagrange sections 12–15 of a file `prepare phase2` has been run on.  Rows
+    are uint64 words in the file's Montgomery form, as read_ptau hands them over; ceremony_power defaults to power.  UNPINNED like the reader: the layout is restated
+    from snarkjs's published format and no file written here has been read by snarkjs yet.  ValueError for a power outside 1..26 and an array whose shape does not
+    match the power."""
+    power = int(powers["power"])
+    if not 1 <= power <= 26:
+        raise ValueError("ptau: power outside 1..26")
+    n2 = 1 << power
+    secs = [(1, struct.pack("<I", 32) + BN254_Q.to_bytes(32, "little") + struct.pack("<II", power, int(powers.get("ceremony_power", power))))]
+    for t, name, size in _PTAU_SECTIONS:
+        points = {"tau_g1": 2 * n2 - 1, "beta_g2": 1}.get(name, n2)
+        a = np.ascontiguousarray(powers[name], dtype="<u8")
+        if a.size != points * size // 8:
+            raise ValueError(f"ptau section {t} ({name}): {a.size * 8} bytes, the power asks for {points * size}")
+        secs.append((t, a.tobytes()))
+    return b"ptau" + struct.pack("<II", 1, len(secs)) + b"".join(struct.pack("<IQ", t, len(body)) + body for t, body in secs)
+
+
+_G2_GENERATOR = ((10857046999023057135944570762232829481370756359578518086990519993285655852781, 11559732032986387107991004021392285783925812861821192530917403151452391805634),
+                 (8495653923123431417604973247489272438418190587263600148770280649306958101930, 4082367875863433681332203403145435568316851327593401208105741076214120093531))
+
+
+def new_powers(power):
+    """The string nobody has contributed to (what snarkjs's `powersoftau new` starts a ceremony with): tau = alpha = beta = 1, so every point of tau_g1, alpha_g1 and
+    beta_g1 is the generator of G1 and every point of tau_g2 and beta_g2 the generator of G2 — read_ptau's dictionary, rows in the file's Montgomery form.  Host,
+    numpy.  Worth nothing until someone contributes (hip.contribute_powers)."""
+    power = int(power)
+    if not 1 <= power <= 26:
+        raise ValueError("new_powers: power outside 1..26")
+    row = lambda coords: np.frombuffer(b"".join((c * (1 << 256) % BN254_Q).to_bytes(32, "little") for c in coords), dtype="<u8")      # noqa: E731
+    g1, g2 = row((1, 2)), row(_G2_GENERATOR[0] + _G2_GENERATOR[1])
+    n2 = 1 << power
+    return {"power": power, "ceremony_power": power, "tau_g1": np.tile(g1, (2 * n2 - 1, 1)), "tau_g2": np.tile(g2, (n2, 1)), "alpha_g1": np.tile(g1, (n2, 1)),
+            "beta_g1": np.tile(g1, (n2, 1)), "beta_g2": np.tile(g2, (1, 1))}
+
+
 def to_nova_columns(r1cs):
     """The matrices with circom wire j moved to nova-snark's column: j = 0 -> the u slot, 1 <= j <= n_pub -> X, the rest -> W.
     -> (n_witness, n_public, A, B, C)."""
@@ -271,7 +309,78 @@ def _verify_key(argv):
     return 1
 
 
+def _new_powers(argv):
+    """new-powers POWER OUT.ptau: the string of tau = alpha = beta = 1 (new_powers) as a .ptau file: the origin of a ceremony.  Host only."""
+    if len(argv) != 3 or not argv[1].isdigit() or not 1 <= int(argv[1]) <= 26:
+        print(USAGE, file=sys.stderr)
+        return 2
+    data = write_ptau(new_powers(int(argv[1])))
+    with open(argv[2], "wb") as fp:
+        fp.write(data)
+    print(f"new-powers: power {int(argv[1])}, every point a generator, {len(data)} bytes -> {argv[2]}")
+    return 0
+
+
+def _contribute_powers(argv):
+    """contribute-powers IN.ptau OUT.ptau RECORDS: one contribution to the string on GPU 0 (hip.contribute_powers: tau', alpha', beta' are drawn here and forgotten);
+    the contributed string goes to OUT.ptau and the 488-byte record is APPENDED to RECORDS (this project's own format, not snarkjs's transcript)."""
+    if len(argv) != 4:
+        print(USAGE, file=sys.stderr)
+        return 2
+    from . import hip
+    with open(argv[1], "rb") as fp:
+        powers = read_ptau(fp.read())
+    sec = [0.0] * 3
+    ctx = hip.Context(0)
+    try:
+        out, rec = hip.contribute_powers(ctx, powers, seconds=sec)
+    finally:
+        ctx.close()
+    data = write_ptau(out)
+    with open(argv[2], "wb") as fp:
+        fp.write(data)
+    with open(argv[3], "ab") as fp:
+        fp.write(bytes(rec))
+        n = fp.tell() // hip.POWCHAIN_RECORD_BYTES
+    print(f"contribute-powers: {argv[1]} -> {argv[2]} (power {int(powers['power'])}, {len(data)} bytes), record {n} appended to {argv[3]} (host {sec[0]:.3f} s, device {sec[1]:.3f} s)")
+    return 0
+
+
+def _verify_powers_contributions(argv):
+    """verify-powers-contributions ORIGIN.ptau FINAL.ptau RECORDS: judges the chain on GPU 0 (hip.verify_powers_contributions), prints the verdict's bit names and the
+    times; exit status 0 accepted, 1 refused.  Accepted means: FINAL.ptau is the powers of one tau with consistent alpha and beta, unknown to everyone if any one
+    contributor forgot their secrets."""
+    if len(argv) != 4:
+        print(USAGE, file=sys.stderr)
+        return 2
+    from . import hip
+    with open(argv[1], "rb") as fp:
+        origin = read_ptau(fp.read())
+    with open(argv[2], "rb") as fp:
+        final = read_ptau(fp.read())
+    records = np.fromfile(argv[3], dtype=np.uint8)
+    sec = [0.0] * 3
+    ctx = hip.Context(0)
+    try:
+        bits, sbits, first = hip.verify_powers_contributions(ctx, origin, final, records, seconds=sec)
+    finally:
+        ctx.close()
+    what = f"{argv[2]} after {records.size // hip.POWCHAIN_RECORD_BYTES} contributions to {argv[1]}"
+    times = f"points {sec[0]:.3f} s, knowledge {sec[1]:.3f} s, the string {sec[2]:.3f} s"
+    if not bits:
+        print(f"verify-powers-contributions: {what}: accepted ({times})")
+        return 0
+    names = " ".join(hip.POWCHAIN_BIT_NAMES[k] for k in range(len(hip.POWCHAIN_BIT_NAMES)) if bits >> k & 1)
+    inner = f"; the string: 0x{sbits:x}: " + "; ".join(hip.powers_problems(sbits)) if sbits else ""
+    at = f"; first: {hip.POWCHAIN_PLACES[first[0]]} {first[1]}" if first[0] else ""
+    print(f"verify-powers-contributions: {what}: REFUSED (0x{bits:x}: {names}): " + "; ".join(hip.powchain_problems(bits)) + f"{inner}{at} ({times})")
+    return 1
+
+
 USAGE = ("usage: python -m vimz_amd.iden3 lagrange FILE.ptau LOGN OUT.npz\n"
+         "       python -m vimz_amd.iden3 new-powers POWER OUT.ptau\n"
+         "       python -m vimz_amd.iden3 contribute-powers IN.ptau OUT.ptau RECORDS\n"
+         "       python -m vimz_amd.iden3 verify-powers-contributions ORIGIN.ptau FINAL.ptau RECORDS\n"
          "       python -m vimz_amd.iden3 decider-key FILE.ptau TRANSFORMATION RESOLUTION OUT.key [--light] [--verify]\n"
          "       python -m vimz_amd.iden3 verify FILE.ptau [POINTS]\n"
          "       python -m vimz_amd.iden3 contribute IN.key OUT.key RECORDS\n"
@@ -283,7 +392,14 @@ def _main(argv):
     """python -m vimz_amd.iden3 lagrange FILE.ptau LOGN OUT.npz: the string's Lagrange bases over the domain of 2^LOGN points (hip.lagrange_from_powers, on GPU 0)
     as an .npz of tau_g1, alpha_g1, beta_g1 (n, 8) and tau_g2 (n, 16) in the file's Montgomery form, with logn.
     python -m vimz_amd.iden3 decider-key ...: _decider_key.  python -m vimz_amd.iden3 verify ...: _verify.
-    python -m vimz_amd.iden3 contribute ... / verify-contributions ... / verify-key ...: _contribute, _verify_contributions, _verify_key."""
+    python -m vimz_amd.iden3 contribute ... / verify-contributions ... / verify-key ...: _contribute, _verify_contributions, _verify_key.
+    python -m vimz_amd.iden3 new-powers ... / contribute-powers ... / verify-powers-contributions ...: _new_powers, _contribute_powers, _verify_powers_contributions."""
+    if argv and argv[0] == "new-powers":
+        return _new_powers(argv)
+    if argv and argv[0] == "contribute-powers":
+        return _contribute_powers(argv)
+    if argv and argv[0] == "verify-powers-contributions":
+        return _verify_powers_contributions(argv)
     if argv and argv[0] == "verify-key":
         return _verify_key(argv)
     if argv and argv[0] == "decider-key":
