@@ -70,6 +70,31 @@ int vimz_test_cross_term_masked(vimz_ctx* ctx, size_t n, const vimz_vec* az1, co
  * producer's S_1 sums do (s1_xy, calls·G points) and is computed again by one ones_launch per row (s1_ref_xy, G points). */
 int vimz_test_msm_rows(vimz_ctx* ctx, const vimz_bases* bases, const uint64_t* scalars, size_t n, size_t row_stride, size_t G, int form, int use_tables,
                        size_t n_ones, int calls, uint64_t* out_xy, uint64_t* s1_xy, uint64_t* s1_ref_xy);
+/* The tail stages of the large MSM (vimz_amd/csrc/msm.hpp) and the four-lane additions under them (ec_mem.hpp) on a caller's arrays, each through the launcher the
+ * product calls (tests/test_gpu_msm_tail.py; the reference and the cases: tests/_msm_tail_ref.py).  curve = VIMZ_CURVE_*, all four.  Points are raw XYZZ slots in the
+ * resident layout of store_xyzz / load_xyzz — 40 words a point: X, Y, ZZ, ZZZ of nine 29-bit limbs in ten words each, Montgomery radix 2^261 — limbs as they stand, no
+ * conversion on the way in or out: any representative inside ec.hpp's bounds (X < 5.3 p, Y < 3.4 p, ZZ, ZZZ < 1.5 p; ZZ = 0: the identity) goes in, the kernel's own
+ * comes back.  Every layout is validated before anything is launched (VIMZ_ERR_INVALID with a message).  calls: that many runs on ONE set of tickets (totals[2],
+ * totals[3], heavy_done), each on the caller's input again; the last run's output comes back.
+ * _scan: blocks (1..256) per-workgroup histograms of nb counters; lds = 1: k_prefix_scan over them (block_hist_out: the exclusive prefixes per block it leaves), lds = 0:
+ * their sums through k_scan.  counts_out nb, bucket_off_out and sub_off_out nb + 1 words, totals_out = totals[0..3] (sub-buckets, entries, the two tickets), heavy_out:
+ * 1 + 65536 + 64 words — the count, the ids (as many as the count, or the cap, says; the rest 0xffffffff), 64 guard words that must come back 0xffffffff.
+ * _combine: k_combine in place over rows (1..16) x n_slots slots of `partial`, sub_off rows x (nb + 1), heavy rows x (1 + n_ids) words: the count word — above 65536: a
+ * list that overflowed — and the ids (each below nb, listed once, of a bucket with more than heavy_min partials), at the product's row strides on the device.
+ * _reduce: mode 0 k_reduce, `windows` sums of nbw buckets each; 1 the same with the plain sums after them (2·windows points a row); 2 k_reduce_planes over one row of
+ * one bucket set, log2(nbw) + 2 sums, the planes' shape from msm_plane_shape.  counts rows x nb, sub_off rows x (nb + 1), nb = nbw·windows.
+ * _tree: count = 0: the sum of m <= 65536 points by k_tree256, level after level as the unit sums chain it (one point out); count 1..16: that many sums of m <= 256
+ * points each by k_tree_rows (count points out).
+ * vimz_test_quad_level: a TEST-ONLY kernel — workgroup s loads slots [256 s, 256 s + 256) into LDS, applies n_levels levels through quad_level (a level: 129 words — count
+ * <= 64, dst[64], src[64]; indices below 256, the dst of a level distinct) or, tree != 0, quad_tree256, and stores all 256 slots to out. */
+int vimz_test_msm_scan(vimz_ctx* ctx, const uint32_t* block_hist, size_t blocks, size_t nb, uint32_t sub, uint32_t heavy_min, int lds, int calls, uint32_t* counts_out,
+                       uint32_t* bucket_off_out, uint32_t* sub_off_out, uint32_t totals_out[4], uint32_t* heavy_out, uint32_t* block_hist_out);
+int vimz_test_msm_combine(vimz_ctx* ctx, int curve, uint32_t* partial, size_t n_slots, const uint32_t* sub_off, size_t nb, const uint32_t* heavy, size_t n_ids, int lane_bits,
+                          uint32_t heavy_min, size_t rows, int calls);
+int vimz_test_msm_reduce(vimz_ctx* ctx, int curve, const uint32_t* partial, size_t n_slots, const uint32_t* counts, const uint32_t* sub_off, uint32_t nbw, size_t windows,
+                         int mode, size_t rows, int calls, uint32_t* sums_out);
+int vimz_test_msm_tree(vimz_ctx* ctx, int curve, const uint32_t* points, size_t m, size_t count, uint32_t* out);
+int vimz_test_quad_level(vimz_ctx* ctx, int curve, const uint32_t* slots, size_t sets, const uint32_t* levels, size_t n_levels, int tree, uint32_t* out);
 /* The decider's kernels (vimz_amd/csrc/groth16.hip) on a caller's shapes, through the functions the set-up and the prover call (tests/test_gpu_g16_kernels.py).
  * The domain of n = 2^logn points, logn in 1..26, with the constants and twiddle tables a key holds: a, b, c and out are HOST arrays of n scalars of 4 words
  * (form = VIMZ_FORM_*, out in the same form).  what = 0: the forward NTT of a; 1: the inverse NTT of a, UNSCALED (n times the inverse); 2: a's evaluations

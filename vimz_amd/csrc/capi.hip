@@ -602,4 +602,232 @@ extern "C" int vimz_test_msm_rows(vimz_ctx* c, const vimz_bases* bases, const ui
   if (e != hipSuccess) return vz_fail(c, VIMZ_ERR_HIP, "vimz_test_msm_rows", e);
   return VIMZ_OK;
 }
+
+// ---- the MSM's tail stages on a caller's arrays (tests/test_gpu_msm_tail.py): every launch through the launcher the product calls (msm.hpp) ------------------
+#include "msm.hpp"
+namespace {
+// device arrays of one hook call: freed on every way out
+struct TailBufs {
+  std::vector<void*> all;
+  ~TailBufs() { for (void* p : all) hipFree(p); }
+  hipError_t get(uint32_t** p, size_t words, int fill = -1) {
+    *p = nullptr;
+    hipError_t e = hipMalloc((void**)p, 4 * (words ? words : 1));
+    if (e != hipSuccess) return e;
+    all.push_back(*p);
+    if (fill >= 0) { e = hipMemset(*p, fill, 4 * (words ? words : 1)); if (e == hipSuccess) e = hipStreamSynchronize(nullptr); }      // (a null-stream fill: msm_api.hpp)
+    return e;
+  }
+};
+static hipError_t tail_up(vimz_ctx* c, uint32_t* d, const uint32_t* h, size_t words) { return words ? hipMemcpyAsync(d, h, 4 * words, hipMemcpyHostToDevice, c->stream) : hipSuccess; }
+static hipError_t tail_down(vimz_ctx* c, uint32_t* h, const uint32_t* d, size_t words) { return words ? hipMemcpyAsync(h, d, 4 * words, hipMemcpyDeviceToHost, c->stream) : hipSuccess; }
+// offsets of nb buckets: monotone, the last one inside an array of n_slots
+static bool tail_offsets_ok(const uint32_t* off, size_t nb, size_t n_slots) {
+  for (size_t b = 0; b < nb; b++) if (off[b] > off[b + 1]) return false;
+  return off[nb] <= n_slots;
+}
+constexpr uint32_t TAIL_HEAVY_GUARD = 64;      // words after the heavy list that a scan must leave alone
+constexpr uint32_t QUAD_LEVEL_WORDS = 129;     // a level of vimz_test_quad_level: count, dst[64], src[64]
+
+// TEST-ONLY kernel: workgroup s loads slots [256 s, 256 s + 256) into LDS, applies the caller's levels through quad_level — the tables are read by the lambdas —
+// or quad_tree256, and stores all 256 slots.
+template <class F>
+__global__ void __launch_bounds__(256) k_test_quad_level(const uint32_t* __restrict__ in, const uint32_t* __restrict__ levels, uint32_t n_levels, int tree, uint32_t* __restrict__ out) {
+  __shared__ XYZZ<F> sh[256];
+  const uint32_t t = threadIdx.x;
+  sh[t] = load_xyzz<F>(in, (size_t)blockIdx.x * 256 + t);
+  __syncthreads();
+  if (tree) quad_tree256<F>(sh);
+  else for (uint32_t l = 0; l < n_levels; l++) {
+    const uint32_t* L = levels + (size_t)QUAD_LEVEL_WORDS * l;
+    quad_level<F>(sh, L[0], [L](uint32_t e) { return L[1 + e]; }, [L](uint32_t e) { return L[65 + e]; });
+  }
+  store_xyzz(out, (size_t)blockIdx.x * 256 + t, sh[t]);
+}
+}  // namespace
+#define TAIL_TRY(x) do { hipError_t _e = (x); if (_e != hipSuccess) { hipStreamSynchronize(c->stream); return vz_fail(c, VIMZ_ERR_HIP, #x, _e); } } while (0)
+
+extern "C" int vimz_test_msm_scan(vimz_ctx* c, const uint32_t* block_hist, size_t blocks, size_t nb, uint32_t sub, uint32_t heavy_min, int lds, int calls, uint32_t* counts_out,
+                                  uint32_t* bucket_off_out, uint32_t* sub_off_out, uint32_t totals_out[4], uint32_t* heavy_out, uint32_t* block_hist_out) {
+  if (!c || !block_hist || !counts_out || !bucket_off_out || !sub_off_out || !totals_out || !heavy_out || (lds != 0 && lds != 1) || (lds && !block_hist_out) || calls < 1)
+    return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_scan: bad argument");
+  if (!blocks || blocks > SORT_BLOCKS || !nb || nb >= (1u << 24) || !sub) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_scan: blocks in 1..256, nb in 1..2^24 - 1, sub >= 1");
+  std::vector<uint32_t> sum(nb, 0u);
+  uint64_t total = 0;
+  for (size_t k = 0; k < blocks; k++) for (size_t g = 0; g < nb; g++) { sum[g] += block_hist[k * nb + g]; total += block_hist[k * nb + g]; }
+  if (total >= (1ull << 31)) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_scan: more than 2^31 - 1 entries");
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  TailBufs B;
+  uint32_t *hist, *counts, *boff, *soff, *totals, *heavy;
+  const size_t heavy_words = 1 + (size_t)MSM_HEAVY_CAP + TAIL_HEAVY_GUARD;
+  TAIL_TRY(B.get(&hist, blocks * nb)); TAIL_TRY(B.get(&counts, nb)); TAIL_TRY(B.get(&boff, nb + 1, 0xff)); TAIL_TRY(B.get(&soff, nb + 1, 0xff));
+  TAIL_TRY(B.get(&totals, MSM_TOTALS_WORDS, 0)); TAIL_TRY(B.get(&heavy, heavy_words, 0xff));
+  for (int call = 0; call < calls; call++) {
+    if (lds) {
+      TAIL_TRY(tail_up(c, hist, block_hist, blocks * nb));
+      launch_prefix_scan(c->stream, hist, (uint32_t)nb, counts, (uint32_t)blocks, heavy, boff, soff, totals, sub, heavy_min, MsmRowStrides(), 1);
+    } else {      // (the fallback sort zeroes the list's count itself: launch_sort)
+      TAIL_TRY(tail_up(c, counts, sum.data(), nb));
+      TAIL_TRY(hipMemsetAsync(heavy, 0, 4, c->stream));
+      launch_scan(c->stream, counts, (uint32_t)nb, boff, soff, totals, sub, heavy, heavy_min);
+    }
+    TAIL_TRY(hipGetLastError());
+    TAIL_TRY(hipStreamSynchronize(c->stream));
+  }
+  TAIL_TRY(tail_down(c, counts_out, counts, nb)); TAIL_TRY(tail_down(c, bucket_off_out, boff, nb + 1)); TAIL_TRY(tail_down(c, sub_off_out, soff, nb + 1));
+  TAIL_TRY(tail_down(c, totals_out, totals, 4)); TAIL_TRY(tail_down(c, heavy_out, heavy, heavy_words));
+  if (lds) TAIL_TRY(tail_down(c, block_hist_out, hist, blocks * nb));
+  TAIL_TRY(hipStreamSynchronize(c->stream));
+  return VIMZ_OK;
+}
+
+extern "C" int vimz_test_msm_combine(vimz_ctx* c, int curve, uint32_t* partial, size_t n_slots, const uint32_t* sub_off, size_t nb, const uint32_t* heavy, size_t n_ids, int lane_bits,
+                                     uint32_t heavy_min, size_t rows, int calls) {
+  if (!c || !partial || !sub_off || !heavy || calls < 1 || !nb || nb >= (1u << 24) || n_slots >= (1u << 24)) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_combine: bad argument");
+  if (curve < VIMZ_CURVE_BN254_G1 || curve > VIMZ_CURVE_VESTA) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_combine: bad curve");
+  if (lane_bits < 0 || lane_bits > 4) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_combine: lane_bits outside 0..4");
+  if (!rows || rows > MSM_ROWS_MAX) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_combine: rows outside 1..16");
+  if (n_ids > MSM_HEAVY_CAP) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_combine: more ids than the heavy list holds");
+  for (size_t r = 0; r < rows; r++) {
+    const uint32_t* off = sub_off + r * (nb + 1); const uint32_t* hv = heavy + r * (1 + n_ids);
+    if (!tail_offsets_ok(off, nb, n_slots)) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_combine: sub_off not monotone or outside partial");
+    if (hv[0] > MSM_HEAVY_CAP) continue;      // an overflowed list is not read
+    if (hv[0] > n_ids) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_combine: the heavy count exceeds the ids given");
+    std::vector<bool> seen(nb, false);
+    for (uint32_t h = 0; h < hv[0]; h++) {
+      const uint32_t b = hv[1 + h];
+      if (b >= nb) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_combine: a heavy bucket id not below nb");
+      if (seen[b] || off[b + 1] - off[b] <= heavy_min) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_combine: a heavy bucket listed twice or not above heavy_min");
+      seen[b] = true;
+    }
+  }
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  const uint32_t G = (uint32_t)rows;
+  const MsmRowStrides rs = msm_row_strides(G, 0, (uint32_t)nb, 0, n_slots, 0);
+  TailBufs B;
+  uint32_t *dp, *doff, *dheavy, *dscr, *ddone;
+  TAIL_TRY(B.get(&dp, rows * XYZZ_WORDS * n_slots)); TAIL_TRY(B.get(&doff, rows * (nb + 1))); TAIL_TRY(B.get(&dheavy, rows * ((size_t)MSM_HEAVY_CAP + 1), 0xff));
+  TAIL_TRY(B.get(&dscr, rows * MsmWorkspace::HEAVY_SCRATCH_WORDS, 0xff)); TAIL_TRY(B.get(&ddone, rows * (size_t)MSM_HEAVY_DONE_WORDS, 0));
+  TAIL_TRY(tail_up(c, doff, sub_off, rows * (nb + 1)));
+  for (size_t r = 0; r < rows; r++) TAIL_TRY(tail_up(c, dheavy + r * ((size_t)MSM_HEAVY_CAP + 1), heavy + r * (1 + n_ids), 1 + n_ids));
+  const int rc = curve_dispatch(curve, [&](auto cv) {
+    typedef typename decltype(cv)::Coord F;
+    for (int call = 0; call < calls; call++) {      // every call folds the caller's partials anew; the tickets are whatever the call before left
+      TAIL_TRY(tail_up(c, dp, partial, rows * XYZZ_WORDS * n_slots));
+      launch_combine<F>(c->stream, dp, doff, (uint32_t)nb, dheavy, dscr, (uint32_t)lane_bits, heavy_min, ddone, rs, G);
+      TAIL_TRY(hipGetLastError());
+      TAIL_TRY(hipStreamSynchronize(c->stream));
+    }
+    return (int)VIMZ_OK;
+  });
+  if (rc) return rc;
+  TAIL_TRY(tail_down(c, partial, dp, rows * XYZZ_WORDS * n_slots));
+  TAIL_TRY(hipStreamSynchronize(c->stream));
+  return VIMZ_OK;
+}
+
+extern "C" int vimz_test_msm_reduce(vimz_ctx* c, int curve, const uint32_t* partial, size_t n_slots, const uint32_t* counts, const uint32_t* sub_off, uint32_t nbw, size_t windows,
+                                    int mode, size_t rows, int calls, uint32_t* sums_out) {
+  if (!c || !partial || !counts || !sub_off || !sums_out || calls < 1 || mode < 0 || mode > 2 || n_slots >= (1u << 24)) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_reduce: bad argument");
+  if (curve < VIMZ_CURVE_BN254_G1 || curve > VIMZ_CURVE_VESTA) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_reduce: bad curve");
+  if (nbw < 2 || nbw > 32768 || (nbw & (nbw - 1))) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_reduce: nbw not a power of two in 2..32768");
+  if (!rows || rows > MSM_ROWS_MAX) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_reduce: rows outside 1..16");
+  uint32_t Pl = 0, Gp = 0;
+  const bool planes_fit = msm_plane_shape(nbw, Pl, Gp);
+  if (!windows || windows > (size_t)MSM_MAX_WINDOWS / 2 || (mode == 2 && (windows != 1 || rows != 1 || !planes_fit)))
+    return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_reduce: windows outside 1..48, or bit planes over anything but one row of one bucket set of 1024 buckets or more");
+  const size_t nb = (size_t)nbw * windows;
+  for (size_t r = 0; r < rows; r++) {
+    const uint32_t* off = sub_off + r * (nb + 1);
+    if (!tail_offsets_ok(off, nb, n_slots)) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_reduce: sub_off not monotone or outside partial");
+    for (size_t b = 0; b < nb; b++) if (counts[r * nb + b] && off[b] >= n_slots) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_reduce: a filled bucket's slot outside partial");
+  }
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  const uint32_t G = (uint32_t)rows;
+  const size_t kout = mode == 2 ? Pl + 2 : mode == 1 ? 2 * windows : windows;
+  const MsmRowStrides rs = msm_row_strides(G, 0, (uint32_t)nb, 0, n_slots, (size_t)XYZZ_WORDS * kout);
+  TailBufs B;
+  uint32_t *dp, *dcnt, *doff, *dout, *dstage, *dtot;
+  TAIL_TRY(B.get(&dp, rows * XYZZ_WORDS * n_slots)); TAIL_TRY(B.get(&dcnt, rows * nb)); TAIL_TRY(B.get(&doff, rows * (nb + 1))); TAIL_TRY(B.get(&dout, rows * XYZZ_WORDS * kout));
+  TAIL_TRY(B.get(&dstage, (size_t)XYZZ_WORDS * 256, 0xff)); TAIL_TRY(B.get(&dtot, MSM_TOTALS_WORDS, 0));
+  TAIL_TRY(tail_up(c, dp, partial, rows * XYZZ_WORDS * n_slots)); TAIL_TRY(tail_up(c, dcnt, counts, rows * nb)); TAIL_TRY(tail_up(c, doff, sub_off, rows * (nb + 1)));
+  const int rc = curve_dispatch(curve, [&](auto cv) {
+    typedef typename decltype(cv)::Coord F;
+    for (int call = 0; call < calls; call++) {
+      TAIL_TRY(hipMemsetAsync(dout, 0xff, 4 * rows * XYZZ_WORDS * kout, c->stream));      // (nothing of an earlier call may pass for this one's result)
+      if (mode == 2) launch_reduce_planes<F>(c->stream, dp, dcnt, doff, nbw, Pl, Gp, dstage, dtot + 3, dout);
+      else launch_reduce<F>(c->stream, dp, dcnt, doff, nbw, (uint32_t)windows, dout, mode == 1 ? dout + (size_t)XYZZ_WORDS * windows : (uint32_t*)nullptr, rs, G);
+      TAIL_TRY(hipGetLastError());
+      TAIL_TRY(hipStreamSynchronize(c->stream));
+    }
+    return (int)VIMZ_OK;
+  });
+  if (rc) return rc;
+  TAIL_TRY(tail_down(c, sums_out, dout, rows * XYZZ_WORDS * kout));
+  TAIL_TRY(hipStreamSynchronize(c->stream));
+  return VIMZ_OK;
+}
+
+extern "C" int vimz_test_msm_tree(vimz_ctx* c, int curve, const uint32_t* points, size_t m, size_t count, uint32_t* out) {
+  if (!c || !points || !out || !m) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_tree: bad argument");
+  if (curve < VIMZ_CURVE_BN254_G1 || curve > VIMZ_CURVE_VESTA) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_tree: bad curve");
+  if (count > MSM_ROWS_MAX) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_tree: more than 16 sums");
+  if (count ? m > 256 : m > 65536) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_tree: more points than the trees take (256 a sum; 65536 for one sum)");
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t sums = count ? count : 1;
+  TailBufs B;
+  uint32_t *din, *dtmp, *dout;
+  TAIL_TRY(B.get(&din, sums * m * XYZZ_WORDS)); TAIL_TRY(B.get(&dtmp, (size_t)XYZZ_WORDS * 256, 0xff)); TAIL_TRY(B.get(&dout, sums * XYZZ_WORDS, 0xff));
+  TAIL_TRY(tail_up(c, din, points, sums * m * XYZZ_WORDS));
+  curve_dispatch(curve, [&](auto cv) {
+    typedef typename decltype(cv)::Coord F;
+    if (!count) launch_tree256<F>(c->stream, din, (uint32_t)m, dtmp, dout);
+    else {
+      OnesDescs ds;
+      for (size_t i = 0; i < 2 * MSM_ROWS_MAX; i++) ds.d[i] = OnesDesc{nullptr, nullptr, i < count ? dout + (size_t)XYZZ_WORDS * i : nullptr, 0};
+      launch_tree_rows<F>(c->stream, din, (uint32_t)m, ds, (uint32_t)count);
+    }
+    return (int)VIMZ_OK;
+  });
+  TAIL_TRY(hipGetLastError());
+  TAIL_TRY(tail_down(c, out, dout, sums * XYZZ_WORDS));
+  TAIL_TRY(hipStreamSynchronize(c->stream));
+  return VIMZ_OK;
+}
+
+extern "C" int vimz_test_quad_level(vimz_ctx* c, int curve, const uint32_t* slots, size_t sets, const uint32_t* levels, size_t n_levels, int tree, uint32_t* out) {
+  if (!c || !slots || !out || !sets || sets > 4096 || (!tree && (!levels || !n_levels)) || n_levels > 64) return fail(c, VIMZ_ERR_INVALID, "vimz_test_quad_level: bad argument");
+  if (curve < VIMZ_CURVE_BN254_G1 || curve > VIMZ_CURVE_VESTA) return fail(c, VIMZ_ERR_INVALID, "vimz_test_quad_level: bad curve");
+  for (size_t l = 0; !tree && l < n_levels; l++) {
+    const uint32_t* L = levels + QUAD_LEVEL_WORDS * l;
+    if (L[0] > 64) return fail(c, VIMZ_ERR_INVALID, "vimz_test_quad_level: more than 64 additions in a level");
+    bool seen[256] = {};
+    for (uint32_t e = 0; e < L[0]; e++) {
+      if (L[1 + e] >= 256 || L[65 + e] >= 256) return fail(c, VIMZ_ERR_INVALID, "vimz_test_quad_level: an index not below 256");
+      if (seen[L[1 + e]]) return fail(c, VIMZ_ERR_INVALID, "vimz_test_quad_level: a destination twice in one level");
+      seen[L[1 + e]] = true;
+    }
+  }
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t words = sets * 256 * XYZZ_WORDS, lw = tree ? 0 : QUAD_LEVEL_WORDS * n_levels;
+  TailBufs B;
+  uint32_t *din, *dlv, *dout;
+  TAIL_TRY(B.get(&din, words)); TAIL_TRY(B.get(&dlv, lw)); TAIL_TRY(B.get(&dout, words, 0xff));
+  TAIL_TRY(tail_up(c, din, slots, words)); TAIL_TRY(tail_up(c, dlv, levels, lw));
+  curve_dispatch(curve, [&](auto cv) {
+    typedef typename decltype(cv)::Coord F;
+    hipLaunchKernelGGL(k_test_quad_level<F>, dim3((unsigned)sets), dim3(256), 0, c->stream, (const uint32_t*)din, (const uint32_t*)dlv, (uint32_t)(tree ? 0 : n_levels), tree, dout);
+    return (int)VIMZ_OK;
+  });
+  TAIL_TRY(hipGetLastError());
+  TAIL_TRY(tail_down(c, out, dout, words));
+  TAIL_TRY(hipStreamSynchronize(c->stream));
+  return VIMZ_OK;
+}
+#undef TAIL_TRY
 #endif  // VIMZ_TESTING

@@ -145,6 +145,14 @@ __device__ __forceinline__ void quad_add_store(XYZZ<F>* __restrict__ sh, uint32_
 // quads has an addition at this level skips the arithmetic (the shuffles are wave-wide, the barriers workgroup-wide): the last five
 // levels of a 256-leaf tree issue on one wave instead of four — the tails are issue-bound per SIMD and, with three proofs sharing
 // the GPU, every slot a waiting wave does not burn goes to another kernel.
+// Contract (what tests/test_gpu_msm_tail.py holds it to, through the test-only kernel of vimz_test_quad_level):
+//   - all 256 threads of the workgroup call it with the same count (it holds two barriers); inside it every lane of a wave with an active quad calls
+//     quad_add_compute and every lane of the workgroup quad_add_store;
+//   - dst(e) for e < count are distinct slots of sh; a slot may be the dst of one quad and the src of another (every source is read before the barrier,
+//     every destination written after it), and dst(e) == src(e) doubles the slot;
+//   - dst and src are called for e < count only.  An inactive quad (e >= count) of a working wave READS sh[0] (it runs the arithmetic on slot 0 with itself,
+//     the shuffles being wave-wide) and writes nothing; a wave without an active quad touches nothing;
+//   - a source that is the identity leaves its destination as it stands, limb for limb; a destination that is the identity becomes a copy of its source, limb for limb.
 template <class F, class Fd, class Fs>
 __device__ __forceinline__ void quad_level(XYZZ<F>* __restrict__ sh, uint32_t count, Fd dst, Fs src) {
   const uint32_t e = threadIdx.x >> 2;

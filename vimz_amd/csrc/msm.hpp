@@ -951,6 +951,64 @@ hipError_t build_tables(hipStream_t stream, const uint32_t* d_bases, size_t n, i
   return hipGetLastError();
 }
 
+// ---- the launches of the tail stages -------------------------------------------------------------------------------------------------------
+// One function per stage, on the caller's arrays: launch_sort / launch_large / the unit sums below issue them on a workspace, the stage tests
+// (vimz_test_msm_scan, _combine, _reduce, _tree: capi.hip, testing library only) on arrays of their own — the grids and arguments stand HERE alone.
+// G rows (blockIdx.y) at the strides of rs; none of them synchronises or checks: the caller reads hipGetLastError().
+// The distances between the row slices of a group's arrays (one row: all zero, as ever), sized by THIS call — scalars and sums lie where the caller says
+// (words), the tickets' arrays — totals, heavy_done — keep fixed strides, so every ticket stays where it was zeroed.
+static inline MsmRowStrides msm_row_strides(uint32_t G, size_t scalar_words, uint32_t nb, size_t entries, size_t max_subs, size_t out_words) {
+  MsmRowStrides rs;
+  if (G > 1) {
+    rs.scalars = scalar_words; rs.block_hist = (size_t)SORT_BLOCKS * nb; rs.sorted = entries; rs.partial = (size_t)XYZZ_WORDS * max_subs;
+    rs.heavy_scratch = MsmWorkspace::HEAVY_SCRATCH_WORDS; rs.out = out_words;
+    rs.counts = nb; rs.offs = nb + 1; rs.totals = MSM_TOTALS_WORDS; rs.heavy = MSM_HEAVY_CAP + 1; rs.heavy_done = MSM_HEAVY_DONE_WORDS;
+  }
+  return rs;
+}
+static inline void launch_prefix_scan(hipStream_t stream, uint32_t* block_hist, uint32_t nb, uint32_t* counts, uint32_t sort_blocks, uint32_t* heavy, uint32_t* bucket_off,
+                                      uint32_t* sub_off, uint32_t* totals, uint32_t sub, uint32_t heavy_min, const MsmRowStrides& rs, uint32_t G) {
+  hipLaunchKernelGGL(k_prefix_scan<0>, dim3((nb + 1023) / 1024, G), dim3(1024), 0, stream, block_hist, nb, counts, sort_blocks, heavy, bucket_off, sub_off,
+                     totals, sub, heavy_min, MSM_HEAVY_CAP, rs);
+}
+static inline void launch_scan(hipStream_t stream, const uint32_t* counts, uint32_t nb, uint32_t* bucket_off, uint32_t* sub_off, uint32_t* totals, uint32_t sub, uint32_t* heavy,
+                               uint32_t heavy_min) {
+  hipLaunchKernelGGL(k_scan<MSM_SUB>, dim3(1), dim3(1024), 0, stream, counts, nb, bucket_off, sub_off, totals, sub, heavy, heavy_min, MSM_HEAVY_CAP);
+}
+template <class F>
+static void launch_combine(hipStream_t stream, uint32_t* partial, const uint32_t* sub_off, uint32_t nb, const uint32_t* heavy, uint32_t* heavy_scratch, uint32_t lane_bits,
+                           uint32_t heavy_min, uint32_t* heavy_done, const MsmRowStrides& rs, uint32_t G) {
+  const unsigned per_wg = 256u >> lane_bits, nbn = (nb + per_wg - 1) / per_wg;
+  hipLaunchKernelGGL(k_combine<F>, dim3(nbn + COMBINE_HEAVY_BLOCKS + COMBINE_SPLIT_BLOCKS, G), dim3(256), 0, stream, partial, sub_off, nb, nbn,
+                     heavy, MSM_HEAVY_CAP, heavy_scratch, lane_bits, heavy_min, heavy_done, rs);
+}
+// `windows` sums of nbw buckets each into window_sums; plain_sums (or nullptr): the windows' unweighted sums too
+template <class F>
+static void launch_reduce(hipStream_t stream, const uint32_t* partial, const uint32_t* counts, const uint32_t* sub_off, uint32_t nbw, uint32_t windows, uint32_t* window_sums,
+                          uint32_t* plain_sums, const MsmRowStrides& rs, uint32_t G) {
+  hipLaunchKernelGGL(k_reduce<F>, dim3(windows, G), dim3(nbw < 256 ? nbw : 256), 0, stream, partial, counts, sub_off, nbw, window_sums, plain_sums, rs);
+}
+// (Pl, Gp: msm_plane_shape(nbw))
+template <class F>
+static void launch_reduce_planes(hipStream_t stream, const uint32_t* partial, const uint32_t* counts, const uint32_t* sub_off, uint32_t nbw, uint32_t Pl, uint32_t Gp,
+                                 uint32_t* plane_scratch, uint32_t* ticket, uint32_t* out) {
+  hipLaunchKernelGGL(k_reduce_planes<F>, dim3((Pl + 2) * Gp), dim3(256), 0, stream, partial, counts, sub_off, nbw, Pl, Gp, nbw / (512u * Gp), plane_scratch, ticket, out);
+}
+// the sum of m (<= 65 536) points at `in` into out[0]: k_tree256 level by level, the levels between them in `tmp` (ceil(m / 256) points; m <= 256: one launch, tmp unused)
+template <class F>
+static void launch_tree256(hipStream_t stream, const uint32_t* in, uint32_t m, uint32_t* tmp, uint32_t* out) {
+  if (m > 256) {
+    hipLaunchKernelGGL(k_tree256<F>, dim3((m + 255) / 256), dim3(256), 0, stream, in, m, tmp);
+    in = tmp; m = (m + 255) / 256;
+  }
+  hipLaunchKernelGGL(k_tree256<F>, dim3(1), dim3(256), 0, stream, in, m, out);
+}
+// `count` sums of m (<= 256) points each, sum i at lvl + i·m points, into ds.d[i].out
+template <class F>
+static void launch_tree_rows(hipStream_t stream, const uint32_t* lvl, uint32_t m, const OnesDescs& ds, uint32_t count) {
+  hipLaunchKernelGGL(k_tree_rows<F>, dim3(count), dim3(256), 0, stream, lvl, m, ds);
+}
+
 // ---- host driver ---------------------------------------------------------------------------------
 // Enqueue the whole pipeline on `stream`; the window sums go straight into `pinned_dst` (host-pinned memory the device can write, msm_sums_out(plan)
 // points: the copy that used to follow — a launch and a dependent hop between the last kernel and the host's wake-up — is gone).  Does not synchronise:
@@ -1036,8 +1094,7 @@ static hipError_t launch_sort(const MsmCall& a, const MsmShape& sh, const MsmRow
                        ws.block_hist, rs);
     VZ_EV(1);
     // per-workgroup histograms -> prefixes and totals, and (last workgroup) the scan: one launch
-    hipLaunchKernelGGL(k_prefix_scan<0>, dim3((pl.nb + 1023) / 1024, G), dim3(1024), 0, a.stream, ws.block_hist, pl.nb, ws.counts, sh.sort_blocks, ws.heavy, ws.bucket_off, ws.sub_off,
-                       ws.totals, sh.sub, sh.heavy_min, MSM_HEAVY_CAP, rs);
+    launch_prefix_scan(a.stream, ws.block_hist, pl.nb, ws.counts, sh.sort_blocks, ws.heavy, ws.bucket_off, ws.sub_off, ws.totals, sh.sub, sh.heavy_min, rs, G);
     VZ_EV(2);
     hipLaunchKernelGGL(k_scatter_lds<S>, dim3(sh.sort_blocks, G), dim3(SORT_THREADS), pl.nb * 4, a.stream, a.d_scalars, a.n, a.scalars_mont, a.split_ones, a.sgn, pl.c, pl.K, sh.bstride, pl.nb,
                        sh.pstride, ws.bucket_off, ws.block_hist, ws.sorted, rs);
@@ -1049,7 +1106,7 @@ static hipError_t launch_sort(const MsmCall& a, const MsmShape& sh, const MsmRow
     VZ_HIP_CHECK(hipMemsetAsync(ws.heavy, 0, 4, a.stream));
     hipLaunchKernelGGL(k_hist<S>, dim3(gs), dim3(256), 0, a.stream, a.d_scalars, a.n, a.scalars_mont, a.split_ones, a.sgn, pl.c, pl.K, sh.bstride, ws.counts);
     VZ_EV(1);
-    hipLaunchKernelGGL(k_scan<MSM_SUB>, dim3(1), dim3(1024), 0, a.stream, ws.counts, pl.nb, ws.bucket_off, ws.sub_off, ws.totals, sh.sub, ws.heavy, sh.heavy_min, MSM_HEAVY_CAP);
+    launch_scan(a.stream, ws.counts, pl.nb, ws.bucket_off, ws.sub_off, ws.totals, sh.sub, ws.heavy, sh.heavy_min);
     VZ_EV(2);
     hipLaunchKernelGGL(k_scatter<S>, dim3(gs), dim3(256), 0, a.stream, a.d_scalars, a.n, a.scalars_mont, a.split_ones, a.sgn, pl.c, pl.K, sh.bstride, sh.pstride,
                        ws.bucket_off, ws.cursor, ws.sorted);
@@ -1074,8 +1131,7 @@ static hipError_t launch_unit_sums(const MsmCall& a, const MsmShape& sh, uint32_
   if (msm_tuning().ones_dense) hipLaunchKernelGGL((k_ones_dense<S, F>), dim3(ONES_THREADS / 256), dim3(256), 0, a.stream, a.d_scalars, a.d_bases, a.n, a.scalars_mont, lvl0);
   else hipLaunchKernelGGL((k_ones_partial<S, F>), dim3(ONES_THREADS / 256), dim3(256), 0, a.stream, a.d_scalars, a.d_bases, a.n, a.scalars_mont, lvl0);
   uint32_t* lvl1 = lvl0 + (size_t)XYZZ_WORDS * ONES_THREADS;
-  hipLaunchKernelGGL(k_tree256<F>, dim3(ONES_THREADS / 256), dim3(256), 0, a.stream, lvl0, ONES_THREADS, lvl1);
-  hipLaunchKernelGGL(k_tree256<F>, dim3(1), dim3(256), 0, a.stream, lvl1, ONES_THREADS / 256, a.wsum + (size_t)XYZZ_WORDS * sh.kout);
+  launch_tree256<F>(a.stream, lvl0, ONES_THREADS, lvl1, a.wsum + (size_t)XYZZ_WORDS * sh.kout);
   return hipSuccess;
 }
 
@@ -1090,30 +1146,17 @@ static hipError_t launch_large(const MsmCall& a, const MsmShape& sh) {
   const uint32_t G = rg ? rg->G : 1u;
   VZ_HIP_CHECK(ws.reserve(pl.nb, sh.entries, sh.max_subs, rg ? std::max<size_t>(G, rg->max_rows) : 1));
   // row slices: strides of this call's sizes (the tickets' arrays — totals, heavy_done — keep fixed strides, so every ticket stays where it was zeroed)
-  MsmRowStrides rs;
-  if (G > 1) {
-    rs.scalars = 8 * rg->scalar_row_stride; rs.block_hist = (size_t)SORT_BLOCKS * pl.nb; rs.sorted = sh.entries; rs.partial = (size_t)XYZZ_WORDS * sh.max_subs;
-    rs.heavy_scratch = MsmWorkspace::HEAVY_SCRATCH_WORDS; rs.out = rg->pinned_row_stride / 4;
-    rs.counts = pl.nb; rs.offs = pl.nb + 1; rs.totals = MSM_TOTALS_WORDS; rs.heavy = MSM_HEAVY_CAP + 1; rs.heavy_done = MSM_HEAVY_DONE_WORDS;
-  }
+  const MsmRowStrides rs = msm_row_strides(G, rg ? 8 * rg->scalar_row_stride : 0, pl.nb, sh.entries, sh.max_subs, rg ? rg->pinned_row_stride / 4 : 0);
   VZ_HIP_CHECK(launch_sort<S>(a, sh, rs, G));
   uint32_t* partial = reinterpret_cast<uint32_t*>(ws.partial);
   hipLaunchKernelGGL(k_accum<F>, dim3((unsigned)((sh.max_subs + 255) / 256), G), dim3(256), 0, a.stream, a.d_bases, ws.sorted, ws.bucket_off, ws.sub_off, pl.nb, ws.totals, partial, sh.sub, rs);
   VZ_EV(4);
-  const unsigned per_wg = 256u >> sh.lane_bits, nbn = (pl.nb + per_wg - 1) / per_wg;
-  hipLaunchKernelGGL(k_combine<F>, dim3(nbn + COMBINE_HEAVY_BLOCKS + COMBINE_SPLIT_BLOCKS, G), dim3(256), 0, a.stream, partial, ws.sub_off, pl.nb, nbn,
-                     (const uint32_t*)ws.heavy, MSM_HEAVY_CAP, ws.heavy_scratch, sh.lane_bits, sh.heavy_min, ws.heavy_done, rs);
+  launch_combine<F>(a.stream, partial, ws.sub_off, pl.nb, ws.heavy, ws.heavy_scratch, sh.lane_bits, sh.heavy_min, ws.heavy_done, rs, G);
   VZ_EV(5);      // (stage 2 of the very heavy buckets: the last of a bucket's workgroups, inside k_combine)
   // sh.kout sums: planes + two plain halves; (R_v, S_v) per virtual window of a shared bucket set; or one per window
-  if (sh.planes) {
-    hipLaunchKernelGGL(k_reduce_planes<F>, dim3((sh.Pl + 2) * sh.Gp), dim3(256), 0, a.stream, (const uint32_t*)partial, (const uint32_t*)ws.counts, (const uint32_t*)ws.sub_off, pl.nbw, sh.Pl, sh.Gp,
-                       pl.nbw / (512u * sh.Gp), ws.plane_scratch, ws.totals + 3, a.wsum);
-  } else if (sh.shared) {
-    hipLaunchKernelGGL(k_reduce<F>, dim3(sh.V, G), dim3(sh.vw < 256 ? sh.vw : 256), 0, a.stream, (const uint32_t*)partial, (const uint32_t*)ws.counts, (const uint32_t*)ws.sub_off, sh.vw, a.wsum,
-                       a.wsum + (size_t)XYZZ_WORDS * sh.V, rs);
-  } else
-    hipLaunchKernelGGL(k_reduce<F>, dim3(pl.K, G), dim3(pl.nbw < 256 ? pl.nbw : 256), 0, a.stream, (const uint32_t*)partial, (const uint32_t*)ws.counts, (const uint32_t*)ws.sub_off, pl.nbw, a.wsum,
-                       (uint32_t*)nullptr, rs);
+  if (sh.planes) launch_reduce_planes<F>(a.stream, partial, ws.counts, ws.sub_off, pl.nbw, sh.Pl, sh.Gp, ws.plane_scratch, ws.totals + 3, a.wsum);
+  else if (sh.shared) launch_reduce<F>(a.stream, partial, ws.counts, ws.sub_off, sh.vw, (uint32_t)sh.V, a.wsum, a.wsum + (size_t)XYZZ_WORDS * sh.V, rs, G);
+  else launch_reduce<F>(a.stream, partial, ws.counts, ws.sub_off, pl.nbw, (uint32_t)pl.K, a.wsum, nullptr, rs, G);
   VZ_EV(6);
   if (a.split_ones) VZ_HIP_CHECK(launch_unit_sums<C>(a, sh, G));
   return hipGetLastError();
@@ -1222,8 +1265,7 @@ hipError_t ones_launch(hipStream_t stream, MsmWorkspace& ws, const uint32_t* d_b
   uint32_t* lvl1 = lvl0 + (size_t)XYZZ_WORDS * ONES_THREADS;
   uint32_t* top = lvl1 + (size_t)XYZZ_WORDS * (ONES_THREADS / 256);      // (inside the spare slots of ones_partial)
   hipLaunchKernelGGL((k_ones_dense<S, F>), dim3(ONES_THREADS / 256), dim3(256), 0, stream, d_scalars, d_bases, n, scalars_mont, lvl0);
-  hipLaunchKernelGGL(k_tree256<F>, dim3(ONES_THREADS / 256), dim3(256), 0, stream, lvl0, ONES_THREADS, lvl1);
-  hipLaunchKernelGGL(k_tree256<F>, dim3(1), dim3(256), 0, stream, lvl1, ONES_THREADS / 256, top);
+  launch_tree256<F>(stream, lvl0, ONES_THREADS, lvl1, top);
   VZ_HIP_CHECK(hipGetLastError());
   return hipMemcpyAsync(pinned_dst, top, 4 * (size_t)XYZZ_WORDS, hipMemcpyDeviceToHost, stream);
 }
@@ -1240,7 +1282,7 @@ hipError_t ones_launch_rows(hipStream_t stream, MsmWorkspace& ws, const OnesDesc
   for (uint32_t i = count; i < 2 * MSM_ROWS_MAX; i++) ds.d[i] = OnesDesc{nullptr, nullptr, nullptr, 0};
   uint32_t* lvl = reinterpret_cast<uint32_t*>(ws.ones_partial);
   hipLaunchKernelGGL((k_ones_dense_rows<S, F>), dim3(ONES_THREADS / 256, count), dim3(256), 0, stream, ds, scalars_mont, lvl);
-  hipLaunchKernelGGL(k_tree_rows<F>, dim3(count), dim3(256), 0, stream, (const uint32_t*)lvl, ONES_THREADS / 256, ds);
+  launch_tree_rows<F>(stream, lvl, ONES_THREADS / 256, ds, count);
   return hipGetLastError();
 }
 template <class C>

@@ -63,6 +63,14 @@ static inline MsmPlan msm_plan(size_t n, int scalar_bits, int c_override) {
 static inline uint32_t msm_vwin(const MsmPlan& p) { return std::min<uint32_t>(p.nbw, MSM_VWIN); }
 static inline int msm_vwindows(const MsmPlan& p) { return (int)(p.nbw / msm_vwin(p)); }
 static inline uint32_t msm_plane_bits(const MsmPlan& p) { uint32_t P = 0; while ((1u << P) < p.nbw) P++; return P; }
+// k_reduce_planes over a bucket set of nbw buckets: Pl = log2 nbw planes, Gp workgroups per plane (256·lpt leaves each, lpt = nbw / (512·Gp)); false where
+// the plane workgroups' partial sums do not fit one tree, or the Pl + 2 sums and a unit sum the pinned buffer
+static inline bool msm_plane_shape(uint32_t nbw, uint32_t& Pl, uint32_t& Gp) {
+  Pl = 0; while ((1u << Pl) < nbw) Pl++;
+  Gp = std::min<uint32_t>(16u, nbw / 1024u);
+  while (Gp > 1 && (Pl + 2) * Gp > 256) Gp >>= 1;
+  return nbw >= 1024 && (1u << Pl) == nbw && (Pl + 2) * Gp <= 256 && (int)Pl + 2 + 1 <= MSM_MAX_WINDOWS;
+}
 static inline int msm_kout(const MsmPlan& p) { return p.tabled == 4 ? (int)msm_plane_bits(p) + 2 : p.tabled == 1 ? 2 * msm_vwindows(p) : p.K; }
 static inline int msm_sums_out(const MsmPlan& p) { return msm_kout(p) + (p.split_ones ? 1 : 0); }      // all sums of the pinned buffer: the unit sum is the last
 
@@ -134,10 +142,8 @@ static inline int msm_shape(MsmShape& out, size_t n, int scalar_bits, int c_over
   if (pl.K + 1 > MSM_MAX_WINDOWS || pl.c > 16 || pl.c < 2) return MSM_SHAPE_INVALID;
   pl.split_ones = split_ones;
   // shared bucket set: as virtual windows (k_reduce), or — VIMZ_TUNE=reduce_planes=1 — by bit planes (k_reduce_planes) where the plane workgroups' partial sums fit one tree
-  s.Pl = msm_plane_bits(pl);
-  s.Gp = std::min<uint32_t>(16u, pl.nbw / 1024u);
-  while (s.Gp > 1 && (s.Pl + 2) * s.Gp > 256) s.Gp >>= 1;
-  s.planes = s.shared && tune.reduce_planes && pl.nbw >= 1024 && (1u << s.Pl) == pl.nbw && (s.Pl + 2) * s.Gp <= 256 && (int)s.Pl + 2 + 1 <= MSM_MAX_WINDOWS;
+  const bool planes_fit = msm_plane_shape(pl.nbw, s.Pl, s.Gp);
+  s.planes = s.shared && tune.reduce_planes && planes_fit;
   if (s.planes) pl.tabled = 4;
   s.lds_sort = (size_t)pl.nb * 4 <= 144 * 1024;      // all buckets' counters fit in one workgroup's LDS at the default window (24 x 1024 x 4 B = 96 KiB): contention-free sort
   if (rg.grouped && (s.planes || s.own || !s.lds_sort)) return MSM_SHAPE_NOT_SUPPORTED;
