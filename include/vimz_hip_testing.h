@@ -95,6 +95,38 @@ int vimz_test_msm_reduce(vimz_ctx* ctx, int curve, const uint32_t* partial, size
                          int mode, size_t rows, int calls, uint32_t* sums_out);
 int vimz_test_msm_tree(vimz_ctx* ctx, int curve, const uint32_t* points, size_t m, size_t count, uint32_t* out);
 int vimz_test_quad_level(vimz_ctx* ctx, int curve, const uint32_t* slots, size_t sets, const uint32_t* levels, size_t n_levels, int tree, uint32_t* out);
+/* The head stages of the MSM (vimz_amd/csrc/msm.hpp) — the digit producers, both counting sorts, k_accum, the unit sums, the two fused paths, the table builders — each
+ * through the function the product calls (tests/test_gpu_msm_head.py; the reference and the cases: tests/_msm_head_ref.py).  Scalars are HOST arrays of 4 words of 64
+ * bits, taken AS THEY LIE in form = VIMZ_FORM_* (no conversion on the way in: a Montgomery word is the caller's own s·2^256 mod p).  Points come back as raw XYZZ slots
+ * (40 words, as in the tail hooks above).  Every layout is validated before anything is launched (VIMZ_ERR_INVALID with a message).  calls: that many runs on ONE
+ * workspace of the hook's own — counters and tickets included —, each on the caller's input again; outputs hold `calls` results, call after call.
+ * _sort: launch_sort over n scalars of `field` (all four) — skip_ones, sgn as load_scalar takes them; window_bits 2..16 and K windows; shared = 0: a bucket set of
+ *   2^(window_bits - 1) buckets per window, 1: one set for all windows; entries are (index + window·pstride) | negative << 31.  lds = 1: k_hist_lds, k_prefix_scan,
+ *   k_scatter_lds over sort_blocks (1..256) workgroups — refused where the nb counters exceed 144 KiB, as msm_shape refuses it; lds = 0: k_hist, k_scan, k_scatter.
+ *   counts_out nb, bucket_off_out and sub_off_out nb + 1, totals_out 4 words (sub-buckets, entries, the two tickets), sorted_out sorted_len >= K·n words a call,
+ *   filled with 0xffffffff before every call.
+ * _accum: launch_accum over rows (1..16) of sorted (rows x entries), bucket_off and sub_off (rows x (nb + 1)) and totals (rows x 16 words; [0]: the sub-buckets to
+ *   accumulate) at the product's row strides, over the points of `bases` (any curve); partial: rows x n_slots slots, in place — the caller's fill shows where nothing was
+ *   written.  Refused: offsets not monotone or outside their arrays, a sub_off that is not the scan of ceil(size / sub), an entry outside the key.
+ * _small: launch_small (k_msm_small; tail = 0: the ticket merge inside it, 1: k_msm_small_sum) over n scalars of the curve's scalar field and the points
+ *   [base_offset, base_offset + n) of the key — use_tables != 0: through the rows 2^(7w)·P_i that vimz_bases_precompute(7) made, row length the key's —, Q chunks of
+ *   `chunk` points: chunk·(Q - 1) < n <= chunk·Q, chunk <= 1536, Q <= 32.  sums_out: K = ceil((bits + 1) / 7) window sums a call.
+ * _fixed: launch_fixed (k_msm_fixed, ceil(n / 1024) workgroups a window) over the key's tables of multiples (vimz_bases_precompute(7)).  sums_out as _small.
+ * _ones: the sum of the points whose scalar is the unit.  kind 0: k_ones_partial, 1: k_ones_dense — launch_ones, then launch_tree256 as the product chains them, one
+ *   row; 2: ones_launch_rows (k_ones_dense_rows + k_tree_rows) over rows (1..32) vectors, row r at scalars + 4·r·row_stride words.  out: one slot a row.
+ * vimz_test_bases_tables: `count` entries of a key's tables, canonical affine, 8 words each, the identity as zeros.  wim: (w, i, m) a entry.  which = 0: point i of
+ *   row w of the window tables made by vimz_bases_precompute(window_bits) (k_build_tables; m ignored); 1: m·(row w, point i), m in 1..64 (k_build_multiples;
+ *   window_bits 7 only). */
+int vimz_test_msm_sort(vimz_ctx* ctx, int field, const uint64_t* scalars, size_t n, int form, int skip_ones, int sgn, int window_bits, int K, int shared, uint32_t pstride, int lds,
+                       uint32_t sort_blocks, uint32_t sub, uint32_t heavy_min, int calls, uint32_t* counts_out, uint32_t* bucket_off_out, uint32_t* sub_off_out, uint32_t* totals_out,
+                       uint32_t* sorted_out, size_t sorted_len);
+int vimz_test_msm_accum(vimz_ctx* ctx, const vimz_bases* bases, const uint32_t* sorted, size_t entries, const uint32_t* bucket_off, const uint32_t* sub_off, const uint32_t* totals,
+                        size_t nb, uint32_t sub, size_t rows, uint32_t* partial, size_t n_slots);
+int vimz_test_msm_small(vimz_ctx* ctx, const vimz_bases* bases, int use_tables, size_t base_offset, const uint64_t* scalars, size_t n, int form, int sgn, uint32_t Q, uint32_t chunk,
+                        int tail, int calls, uint32_t* sums_out);
+int vimz_test_msm_fixed(vimz_ctx* ctx, const vimz_bases* bases, size_t base_offset, const uint64_t* scalars, size_t n, int form, int sgn, int calls, uint32_t* sums_out);
+int vimz_test_msm_ones(vimz_ctx* ctx, const vimz_bases* bases, const uint64_t* scalars, size_t n, size_t row_stride, size_t rows, int form, int kind, uint32_t* out);
+int vimz_test_bases_tables(vimz_ctx* ctx, const vimz_bases* bases, int window_bits, int which, const uint32_t* wim, size_t count, uint64_t* out_xy);
 /* The decider's kernels (vimz_amd/csrc/groth16.hip) on a caller's shapes, through the functions the set-up and the prover call (tests/test_gpu_g16_kernels.py).
  * The domain of n = 2^logn points, logn in 1..26, with the constants and twiddle tables a key holds: a, b, c and out are HOST arrays of n scalars of 4 words
  * (form = VIMZ_FORM_*, out in the same form).  what = 0: the forward NTT of a; 1: the inverse NTT of a, UNSCALED (n times the inverse); 2: a's evaluations

@@ -829,5 +829,242 @@ extern "C" int vimz_test_quad_level(vimz_ctx* c, int curve, const uint32_t* slot
   TAIL_TRY(hipStreamSynchronize(c->stream));
   return VIMZ_OK;
 }
+
+// ---- the MSM's head stages on a caller's input (tests/test_gpu_msm_head.py; the reference and the cases: tests/_msm_head_ref.py): launch_sort, launch_small and
+// launch_fixed with an MsmCall and an MsmShape filled by hand on a workspace of the hook's own; launch_accum, launch_ones, ones_launch_rows on arrays of its own --------
+namespace {
+struct WorkspaceGuard {      // the hook's own workspace: released on every way out
+  MsmWorkspace ws;
+  ~WorkspaceGuard() { ws.release(); }
+};
+struct PinnedGuard {
+  void* p = nullptr;
+  ~PinnedGuard() { if (p) hipHostFree(p); }
+};
+// the tables vimz_bases_precompute(7) made for the whole key (rows 2^(7w)·P_i, every multiple of them), or nullptr
+static const vimz_small_tables* head_small_tables(const vimz_bases* b) {
+  vimz_bases* bm = const_cast<vimz_bases*>(b);
+  std::lock_guard<std::mutex> g(bm->small_mu);
+  for (auto& t : bm->small) if (t.offset == 0 && t.n == b->n && t.rows) return &t;
+  return nullptr;
+}
+static int head_small_windows(int curve) {
+  int K = 0;
+  curve_dispatch(curve, [&](auto cv) { typedef decltype(cv) C; K = (C::Scalar::Params::BITS + SMALL_C) / SMALL_C; return (int)VIMZ_OK; });
+  return K;
+}
+}  // namespace
+
+extern "C" int vimz_test_msm_sort(vimz_ctx* c, int field, const uint64_t* scalars, size_t n, int form, int skip_ones, int sgn, int window_bits, int K, int shared, uint32_t pstride,
+                                  int lds, uint32_t sort_blocks, uint32_t sub, uint32_t heavy_min, int calls, uint32_t* counts_out, uint32_t* bucket_off_out, uint32_t* sub_off_out,
+                                  uint32_t* totals_out, uint32_t* sorted_out, size_t sorted_len) {
+  if (!c || !scalars || !counts_out || !bucket_off_out || !sub_off_out || !totals_out || !sorted_out || calls < 1 || (lds != 0 && lds != 1) || (shared != 0 && shared != 1) ||
+      (form != VIMZ_FORM_CANONICAL && form != VIMZ_FORM_MONTGOMERY))
+    return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_sort: bad argument");
+  if (field < VIMZ_FIELD_BN254_FR || field > VIMZ_FIELD_VESTA_FQ) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_sort: bad field");
+  if (window_bits < 2 || window_bits > 16) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_sort: window bits outside 2..16");
+  if (K < 1 || K > 128 || !n || n >= (1u << 24) || !sub) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_sort: K in 1..128, n in 1..2^24 - 1, sub >= 1");
+  if (!sort_blocks || sort_blocks > SORT_BLOCKS) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_sort: sort_blocks outside 1..256");
+  const uint32_t nbw = 1u << (window_bits - 1);
+  const size_t nb = shared ? nbw : (size_t)nbw * K;
+  if (lds && nb * 4 > 144 * 1024) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_sort: the counters of the LDS sort do not fit 144 KiB");
+  if (sorted_len < (size_t)K * n || sorted_len >= (1u << 31)) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_sort: `sorted` shorter than K·n entries (or 2^31 and more)");
+  if (n + (size_t)K * pstride >= (1u << 31)) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_sort: an entry would not fit 31 bits");
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  WorkspaceGuard W;
+  TailBufs B;
+  uint32_t* dsc;
+  TAIL_TRY(W.ws.reserve((uint32_t)nb, sorted_len, 1));
+  TAIL_TRY(B.get(&dsc, 8 * n));
+  TAIL_TRY(tail_up(c, dsc, reinterpret_cast<const uint32_t*>(scalars), 8 * n));
+  MsmShape sh;
+  sh.plan.c = window_bits; sh.plan.K = K; sh.plan.nbw = nbw; sh.plan.nb = (uint32_t)nb; sh.plan.split_ones = skip_ones; sh.plan.tabled = 0;
+  sh.lds_sort = lds != 0; sh.shared = shared != 0; sh.sub = sub; sh.entries = sorted_len; sh.max_subs = 1; sh.sort_blocks = sort_blocks; sh.heavy_min = heavy_min;
+  sh.bstride = shared ? 0u : nbw; sh.pstride = pstride;
+  const MsmCall a{c->stream, W.ws, nullptr, dsc, n, form == VIMZ_FORM_MONTGOMERY, sgn, skip_ones, nullptr, nullptr, nullptr, nullptr};
+  return field_dispatch(field, [&](auto f) {
+    typedef decltype(f) S;
+    for (int call = 0; call < calls; call++) {      // every call sorts the caller's scalars anew; the ticket (totals[2]) is whatever the call before left
+      TAIL_TRY(hipMemsetAsync(W.ws.sorted, 0xff, 4 * sorted_len, c->stream));
+      TAIL_TRY(launch_sort<S>(a, sh, MsmRowStrides(), 1));
+      TAIL_TRY(hipGetLastError());
+      TAIL_TRY(tail_down(c, counts_out + (size_t)call * nb, W.ws.counts, nb)); TAIL_TRY(tail_down(c, bucket_off_out + (size_t)call * (nb + 1), W.ws.bucket_off, nb + 1));
+      TAIL_TRY(tail_down(c, sub_off_out + (size_t)call * (nb + 1), W.ws.sub_off, nb + 1)); TAIL_TRY(tail_down(c, totals_out + 4 * (size_t)call, W.ws.totals, 4));
+      TAIL_TRY(tail_down(c, sorted_out + (size_t)call * sorted_len, W.ws.sorted, sorted_len));
+      TAIL_TRY(hipStreamSynchronize(c->stream));
+    }
+    return (int)VIMZ_OK;
+  });
+}
+
+extern "C" int vimz_test_msm_accum(vimz_ctx* c, const vimz_bases* bases, const uint32_t* sorted, size_t entries, const uint32_t* bucket_off, const uint32_t* sub_off,
+                                   const uint32_t* totals, size_t nb, uint32_t sub, size_t rows, uint32_t* partial, size_t n_slots) {
+  if (!c || !bases || !bases->n || !sorted || !bucket_off || !sub_off || !totals || !partial || !nb || nb >= (1u << 24) || !sub || !entries || entries >= (1u << 31) || !n_slots ||
+      n_slots >= (1u << 24))
+    return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_accum: bad argument");
+  if (!rows || rows > MSM_ROWS_MAX) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_accum: rows outside 1..16");
+  for (size_t r = 0; r < rows; r++) {
+    const uint32_t* bo = bucket_off + r * (nb + 1); const uint32_t* so = sub_off + r * (nb + 1); const uint32_t* srt = sorted + r * entries;
+    if (bo[0] || so[0] || !tail_offsets_ok(bo, nb, entries) || !tail_offsets_ok(so, nb, n_slots))
+      return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_accum: offsets that do not start at zero, are not monotone or end outside their array");
+    for (size_t b = 0; b < nb; b++)
+      if (so[b + 1] - so[b] != (bo[b + 1] - bo[b] + sub - 1) / sub) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_accum: sub_off is not the scan of ceil(bucket size / sub)");
+    if (totals[r * MSM_TOTALS_WORDS] > so[nb]) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_accum: totals[0] above the number of sub-buckets");
+    for (uint32_t e = 0; e < bo[nb]; e++) if ((srt[e] & 0x7fffffffu) >= bases->n) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_accum: an entry's point outside the key");
+  }
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  const uint32_t G = (uint32_t)rows;
+  const MsmRowStrides rs = msm_row_strides(G, 0, (uint32_t)nb, entries, n_slots, 0);
+  TailBufs B;
+  uint32_t *dsrt, *dbo, *dso, *dtot, *dp;
+  TAIL_TRY(B.get(&dsrt, rows * entries)); TAIL_TRY(B.get(&dbo, rows * (nb + 1))); TAIL_TRY(B.get(&dso, rows * (nb + 1))); TAIL_TRY(B.get(&dtot, rows * MSM_TOTALS_WORDS));
+  TAIL_TRY(B.get(&dp, rows * XYZZ_WORDS * n_slots));
+  TAIL_TRY(tail_up(c, dsrt, sorted, rows * entries)); TAIL_TRY(tail_up(c, dbo, bucket_off, rows * (nb + 1))); TAIL_TRY(tail_up(c, dso, sub_off, rows * (nb + 1)));
+  TAIL_TRY(tail_up(c, dtot, totals, rows * MSM_TOTALS_WORDS)); TAIL_TRY(tail_up(c, dp, partial, rows * XYZZ_WORDS * n_slots));
+  curve_dispatch(bases->curve, [&](auto cv) {
+    typedef typename decltype(cv)::Coord F;
+    launch_accum<F>(c->stream, bases->d, dsrt, dbo, dso, (uint32_t)nb, dtot, dp, sub, n_slots, rs, G);
+    return (int)VIMZ_OK;
+  });
+  TAIL_TRY(hipGetLastError());
+  TAIL_TRY(tail_down(c, partial, dp, rows * XYZZ_WORDS * n_slots));
+  TAIL_TRY(hipStreamSynchronize(c->stream));
+  return VIMZ_OK;
+}
+
+// what the two fused hooks share: the scalars up, `calls` launches by `launch` into a pinned buffer of the hook's own (as the product's callers hand one in), K sums a call out
+template <class Launch>
+static int head_fused_run(vimz_ctx* c, const uint64_t* scalars, size_t n, int K, int calls, uint32_t* sums_out, Launch launch) {
+  WorkspaceGuard W;
+  TailBufs B;
+  PinnedGuard pin;
+  uint32_t* dsc;
+  const size_t out_words = (size_t)XYZZ_WORDS * K;
+  TAIL_TRY(hipHostMalloc(&pin.p, 4 * out_words));
+  TAIL_TRY(B.get(&dsc, 8 * n));
+  TAIL_TRY(tail_up(c, dsc, reinterpret_cast<const uint32_t*>(scalars), 8 * n));
+  for (int call = 0; call < calls; call++) {      // every call on the caller's scalars again; the windows' tickets are whatever the call before left
+    TAIL_TRY(hipStreamSynchronize(c->stream));
+    memset(pin.p, 0xff, 4 * out_words);           // (nothing of an earlier call may pass for this one's result)
+    TAIL_TRY(launch(W.ws, dsc, reinterpret_cast<uint32_t*>(pin.p)));
+    TAIL_TRY(hipStreamSynchronize(c->stream));
+    memcpy(sums_out + (size_t)call * out_words, pin.p, 4 * out_words);
+  }
+  return VIMZ_OK;
+}
+
+extern "C" int vimz_test_msm_small(vimz_ctx* c, const vimz_bases* bases, int use_tables, size_t base_offset, const uint64_t* scalars, size_t n, int form, int sgn, uint32_t Q,
+                                   uint32_t chunk, int tail, int calls, uint32_t* sums_out) {
+  if (!c || !bases || !scalars || !sums_out || !n || calls < 1 || (tail != 0 && tail != 1) || (form != VIMZ_FORM_CANONICAL && form != VIMZ_FORM_MONTGOMERY))
+    return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_small: bad argument");
+  if (base_offset > bases->n || n > bases->n - base_offset) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_small: the scalars reach past the key");
+  if (!Q || Q > SMALL_MAXQ) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_small: Q outside 1..32");
+  if (!chunk || chunk > SMALL_CHUNK) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_small: chunk outside 1..1536");
+  if ((size_t)chunk * (Q - 1) >= n || n > (size_t)chunk * Q) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_small: not chunk·(Q - 1) < n <= chunk·Q");
+  const vimz_small_tables* st = use_tables ? head_small_tables(bases) : nullptr;
+  if (use_tables && !st) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_small: the key has no tables of the fused path (vimz_bases_precompute(7))");
+  const int K = head_small_windows(bases->curve);
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  MsmShape sh;
+  sh.path = MSM_PATH_SMALL; sh.plan.c = SMALL_C; sh.plan.K = K; sh.plan.nbw = SMALL_NBW; sh.plan.nb = SMALL_NBW * (uint32_t)K; sh.plan.split_ones = 0; sh.plan.tabled = st ? 2 : 0;
+  sh.Q = Q; sh.chunk = chunk; sh.kout = K;
+  BaseTables tb{nullptr, 0, 0, 0, 0};
+  if (st) tb = BaseTables{st->rows, st->n, base_offset, st->c, st->K, 0, st->mult};
+  return curve_dispatch(bases->curve, [&](auto cv) {
+    typedef decltype(cv) C;
+    return head_fused_run(c, scalars, n, K, calls, sums_out, [&](MsmWorkspace& ws, const uint32_t* dsc, uint32_t* pinned) {
+      const MsmCall a{c->stream, ws, bases->d + (size_t)AFFINE_WORDS * base_offset, dsc, n, form == VIMZ_FORM_MONTGOMERY, sgn, 0, pinned, nullptr, st ? &tb : nullptr, nullptr};
+      return launch_small<C>(a, sh, tail != 0);
+    });
+  });
+}
+
+extern "C" int vimz_test_msm_fixed(vimz_ctx* c, const vimz_bases* bases, size_t base_offset, const uint64_t* scalars, size_t n, int form, int sgn, int calls, uint32_t* sums_out) {
+  if (!c || !bases || !scalars || !sums_out || !n || calls < 1 || (form != VIMZ_FORM_CANONICAL && form != VIMZ_FORM_MONTGOMERY))
+    return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_fixed: bad argument");
+  if (base_offset > bases->n || n > bases->n - base_offset) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_fixed: the scalars reach past the key");
+  if (n > (size_t)FIXED_CHUNK * FIXED_MAXQ) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_fixed: more than 64 workgroups a window");
+  const vimz_small_tables* st = head_small_tables(bases);
+  if (!st || !st->mult) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_fixed: the key has no tables of multiples (vimz_bases_precompute(7))");
+  const int K = head_small_windows(bases->curve);
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  MsmShape sh;
+  sh.path = MSM_PATH_FIXED; sh.plan.c = SMALL_C; sh.plan.K = K; sh.plan.nbw = SMALL_NBW; sh.plan.nb = SMALL_NBW * (uint32_t)K; sh.plan.split_ones = 0; sh.plan.tabled = 2;
+  sh.Qf = (uint32_t)((n + FIXED_CHUNK - 1) / FIXED_CHUNK); sh.kout = K;
+  const BaseTables tb{st->rows, st->n, base_offset, st->c, st->K, 0, st->mult};
+  return curve_dispatch(bases->curve, [&](auto cv) {
+    typedef decltype(cv) C;
+    return head_fused_run(c, scalars, n, K, calls, sums_out, [&](MsmWorkspace& ws, const uint32_t* dsc, uint32_t* pinned) {
+      const MsmCall a{c->stream, ws, bases->d + (size_t)AFFINE_WORDS * base_offset, dsc, n, form == VIMZ_FORM_MONTGOMERY, sgn, 0, pinned, nullptr, &tb, nullptr};
+      return launch_fixed<C>(a, sh);
+    });
+  });
+}
+
+extern "C" int vimz_test_msm_ones(vimz_ctx* c, const vimz_bases* bases, const uint64_t* scalars, size_t n, size_t row_stride, size_t rows, int form, int kind, uint32_t* out) {
+  if (!c || !bases || !scalars || !out || !n || row_stride < n || kind < 0 || kind > 2 || (form != VIMZ_FORM_CANONICAL && form != VIMZ_FORM_MONTGOMERY))
+    return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_ones: bad argument");
+  if (n > bases->n || n >= (1u << 31)) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_ones: more scalars than the key has points");
+  if (!rows || rows > (kind == 2 ? 2 * MSM_ROWS_MAX : 1u)) return fail(c, VIMZ_ERR_INVALID, "vimz_test_msm_ones: rows outside 1..32 (kinds 0 and 1: one row)");
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  const int mont = form == VIMZ_FORM_MONTGOMERY;
+  const size_t sc_words = 8 * ((rows - 1) * row_stride + n);
+  WorkspaceGuard W;
+  TailBufs B;
+  uint32_t *dsc, *dlvl, *dout;
+  TAIL_TRY(B.get(&dsc, sc_words)); TAIL_TRY(B.get(&dlvl, (size_t)XYZZ_WORDS * (ONES_THREADS + ONES_THREADS / 256), 0xff)); TAIL_TRY(B.get(&dout, rows * XYZZ_WORDS, 0xff));
+  TAIL_TRY(tail_up(c, dsc, reinterpret_cast<const uint32_t*>(scalars), sc_words));
+  const int rc = curve_dispatch(bases->curve, [&](auto cv) {
+    typedef decltype(cv) C;
+    typedef typename C::Coord F;
+    typedef typename C::Scalar S;
+    if (kind == 2) {
+      OnesDesc ds[2 * MSM_ROWS_MAX];
+      for (size_t r = 0; r < rows; r++) ds[r] = OnesDesc{dsc + 8 * r * row_stride, bases->d, dout + (size_t)XYZZ_WORDS * r, n};
+      TAIL_TRY(ones_launch_rows<C>(c->stream, W.ws, ds, (uint32_t)rows, mont));
+    } else {      // the partial sums, then the tree the product runs over them
+      launch_ones<S, F>(c->stream, kind == 1, dsc, bases->d, n, mont, dlvl);
+      launch_tree256<F>(c->stream, dlvl, ONES_THREADS, dlvl + (size_t)XYZZ_WORDS * ONES_THREADS, dout);
+    }
+    return (int)VIMZ_OK;
+  });
+  if (rc) return rc;
+  TAIL_TRY(hipGetLastError());
+  TAIL_TRY(tail_down(c, out, dout, rows * XYZZ_WORDS));
+  TAIL_TRY(hipStreamSynchronize(c->stream));
+  return VIMZ_OK;
+}
+
+extern "C" int vimz_test_bases_tables(vimz_ctx* c, const vimz_bases* bases, int window_bits, int which, const uint32_t* wim, size_t count, uint64_t* out_xy) {
+  if (!c || !bases || !wim || !out_xy || !count || count > 4096 || (which != 0 && which != 1)) return fail(c, VIMZ_ERR_INVALID, "vimz_test_bases_tables: bad argument");
+  const vimz_small_tables* st = window_bits == SMALL_C ? head_small_tables(bases) : nullptr;
+  const uint32_t* src = nullptr; size_t n = bases->n; int K = 0;
+  if (window_bits == SMALL_C) { if (st) { src = which ? st->mult : st->rows; K = st->K; } }
+  else if (!which && bases->tables && bases->table_c == window_bits) { src = bases->tables; K = bases->table_K; }
+  if (!src) return fail(c, VIMZ_ERR_INVALID, "vimz_test_bases_tables: the key has no such tables (window tables of window_bits; multiples: window_bits 7 only)");
+  for (size_t k = 0; k < count; k++)
+    if (wim[3 * k] >= (uint32_t)K || wim[3 * k + 1] >= n || (which && (!wim[3 * k + 2] || wim[3 * k + 2] > SMALL_NBW)))
+      return fail(c, VIMZ_ERR_INVALID, "vimz_test_bases_tables: an entry outside the tables (w below K, i below n, m in 1..64)");
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  TailBufs B;
+  uint32_t *dsel, *dstd;
+  TAIL_TRY(B.get(&dsel, (size_t)AFFINE_WORDS * count)); TAIL_TRY(B.get(&dstd, 16 * count));
+  for (size_t k = 0; k < count; k++) {
+    size_t idx = (size_t)wim[3 * k] * n + wim[3 * k + 1];
+    if (which) idx = idx * SMALL_NBW + (wim[3 * k + 2] - 1);
+    TAIL_TRY(hipMemcpyAsync(dsel + (size_t)AFFINE_WORDS * k, src + (size_t)AFFINE_WORDS * idx, 4 * (size_t)AFFINE_WORDS, hipMemcpyDeviceToDevice, c->stream));
+  }
+  field_dispatch(curve_base_field(bases->curve), [&](auto f) { typedef decltype(f) F; launch_points_from_internal<F>(c->stream, dsel, 1, dstd, count); return (int)VIMZ_OK; });
+  TAIL_TRY(hipGetLastError());
+  TAIL_TRY(tail_down(c, reinterpret_cast<uint32_t*>(out_xy), dstd, 16 * count));
+  TAIL_TRY(hipStreamSynchronize(c->stream));
+  return VIMZ_OK;
+}
 #undef TAIL_TRY
 #endif  // VIMZ_TESTING

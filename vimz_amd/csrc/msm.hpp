@@ -953,7 +953,8 @@ hipError_t build_tables(hipStream_t stream, const uint32_t* d_bases, size_t n, i
 
 // ---- the launches of the tail stages -------------------------------------------------------------------------------------------------------
 // One function per stage, on the caller's arrays: launch_sort / launch_large / the unit sums below issue them on a workspace, the stage tests
-// (vimz_test_msm_scan, _combine, _reduce, _tree: capi.hip, testing library only) on arrays of their own — the grids and arguments stand HERE alone.
+// (vimz_test_msm_scan, _combine, _reduce, _tree, _accum, _ones: capi.hip, testing library only) on arrays of their own — the grids and arguments stand HERE alone.
+// (The head's stage tests — vimz_test_msm_sort, _small, _fixed — call launch_sort, launch_small and launch_fixed further down with an MsmCall and an MsmShape filled by hand.)
 // G rows (blockIdx.y) at the strides of rs; none of them synchronises or checks: the caller reads hipGetLastError().
 // The distances between the row slices of a group's arrays (one row: all zero, as ever), sized by THIS call — scalars and sums lie where the caller says
 // (words), the tickets' arrays — totals, heavy_done — keep fixed strides, so every ticket stays where it was zeroed.
@@ -994,6 +995,18 @@ static void launch_reduce_planes(hipStream_t stream, const uint32_t* partial, co
                                  uint32_t* plane_scratch, uint32_t* ticket, uint32_t* out) {
   hipLaunchKernelGGL(k_reduce_planes<F>, dim3((Pl + 2) * Gp), dim3(256), 0, stream, partial, counts, sub_off, nbw, Pl, Gp, nbw / (512u * Gp), plane_scratch, ticket, out);
 }
+// one thread per sub-bucket of `sorted` — totals[0] of them a row, at most max_subs — into `partial`
+template <class F>
+static void launch_accum(hipStream_t stream, const uint32_t* bases, const uint32_t* sorted, const uint32_t* bucket_off, const uint32_t* sub_off, uint32_t nb, const uint32_t* totals,
+                         uint32_t* partial, uint32_t sub, size_t max_subs, const MsmRowStrides& rs, uint32_t G) {
+  hipLaunchKernelGGL(k_accum<F>, dim3((unsigned)((max_subs + 255) / 256), G), dim3(256), 0, stream, bases, sorted, bucket_off, sub_off, nb, totals, partial, sub, rs);
+}
+// ONES_THREADS partial sums of the bases whose scalar is the unit into lvl0, by the compacted walk (dense) or by one strided loop a thread; launch_tree256 finishes them
+template <class S, class F>
+static void launch_ones(hipStream_t stream, bool dense, const uint32_t* scalars, const uint32_t* bases, size_t n, int mont, uint32_t* lvl0) {
+  if (dense) hipLaunchKernelGGL((k_ones_dense<S, F>), dim3(ONES_THREADS / 256), dim3(256), 0, stream, scalars, bases, n, mont, lvl0);
+  else hipLaunchKernelGGL((k_ones_partial<S, F>), dim3(ONES_THREADS / 256), dim3(256), 0, stream, scalars, bases, n, mont, lvl0);
+}
 // the sum of m (<= 65 536) points at `in` into out[0]: k_tree256 level by level, the levels between them in `tmp` (ceil(m / 256) points; m <= 256: one launch, tmp unused)
 template <class F>
 static void launch_tree256(hipStream_t stream, const uint32_t* in, uint32_t m, uint32_t* tmp, uint32_t* out) {
@@ -1030,6 +1043,10 @@ static inline bool msm_no_small() {      // (tables of the fused path are then i
   static const bool no_small = getenv("VIMZ_DEBUG_NO_SMALL_MSM") != nullptr;
   return no_small;
 }
+static inline bool msm_small_sum_kernel() {      // (read once, as ever: the fused small path's tail as a kernel of its own)
+  static const bool sum_kernel = getenv("VIMZ_DEBUG_SMALL_SUM_KERNEL") != nullptr;
+  return sum_kernel;
+}
 #define VZ_EV(i) do { if (a.ev) VZ_HIP_CHECK(hipEventRecord(a.ev[i], a.stream)); } while (0)
 
 // every multiple of the key slice resident: the digits select their points
@@ -1046,9 +1063,10 @@ static hipError_t launch_fixed(const MsmCall& a, const MsmShape& sh) {
   return hipGetLastError();
 }
 
-// the fused single launch; with tables made for it (plan.tabled == 2) window w reads row w of them
+// the fused single launch; with tables made for it (plan.tabled == 2) window w reads row w of them.  sum_kernel: the chunk results of a window summed by
+// k_msm_small_sum, not by the last of its workgroups (the product: msm_small_sum_kernel())
 template <class C>
-static hipError_t launch_small(const MsmCall& a, const MsmShape& sh) {
+static hipError_t launch_small(const MsmCall& a, const MsmShape& sh, bool sum_kernel) {
   typedef typename C::Coord F;
   typedef typename C::Scalar S;
   VZ_HIP_CHECK(a.ws.reserve_small());
@@ -1056,7 +1074,6 @@ static hipError_t launch_small(const MsmCall& a, const MsmShape& sh) {
   uint32_t* chunk_out = done + 128;
   const bool small_tb = sh.plan.tabled == 2;
   for (int i = 0; i < 4; i++) VZ_EV(i);
-  static const bool sum_kernel = getenv("VIMZ_DEBUG_SMALL_SUM_KERNEL") != nullptr;
   hipLaunchKernelGGL((k_msm_small<S, F>), dim3(sh.plan.K, sh.Q), dim3(SMALL_THREADS), 0, a.stream, a.d_bases, a.d_scalars, (uint32_t)a.n, a.scalars_mont, a.sgn, sh.Q, sh.chunk, chunk_out,
                      sum_kernel ? (uint32_t*)nullptr : done, a.wsum,
                      small_tb ? a.tb->d + (size_t)AFFINE_WORDS * a.tb->offset : (const uint32_t*)nullptr, small_tb ? (uint32_t)a.tb->n_total : 0u);
@@ -1128,8 +1145,7 @@ static hipError_t launch_unit_sums(const MsmCall& a, const MsmShape& sh, uint32_
     return ones_launch_rows<C>(a.stream, a.ws, ds, G + rg->n_extra, a.scalars_mont);
   }
   uint32_t* lvl0 = reinterpret_cast<uint32_t*>(a.ws.ones_partial);
-  if (msm_tuning().ones_dense) hipLaunchKernelGGL((k_ones_dense<S, F>), dim3(ONES_THREADS / 256), dim3(256), 0, a.stream, a.d_scalars, a.d_bases, a.n, a.scalars_mont, lvl0);
-  else hipLaunchKernelGGL((k_ones_partial<S, F>), dim3(ONES_THREADS / 256), dim3(256), 0, a.stream, a.d_scalars, a.d_bases, a.n, a.scalars_mont, lvl0);
+  launch_ones<S, F>(a.stream, msm_tuning().ones_dense != 0, a.d_scalars, a.d_bases, a.n, a.scalars_mont, lvl0);
   uint32_t* lvl1 = lvl0 + (size_t)XYZZ_WORDS * ONES_THREADS;
   launch_tree256<F>(a.stream, lvl0, ONES_THREADS, lvl1, a.wsum + (size_t)XYZZ_WORDS * sh.kout);
   return hipSuccess;
@@ -1149,7 +1165,7 @@ static hipError_t launch_large(const MsmCall& a, const MsmShape& sh) {
   const MsmRowStrides rs = msm_row_strides(G, rg ? 8 * rg->scalar_row_stride : 0, pl.nb, sh.entries, sh.max_subs, rg ? rg->pinned_row_stride / 4 : 0);
   VZ_HIP_CHECK(launch_sort<S>(a, sh, rs, G));
   uint32_t* partial = reinterpret_cast<uint32_t*>(ws.partial);
-  hipLaunchKernelGGL(k_accum<F>, dim3((unsigned)((sh.max_subs + 255) / 256), G), dim3(256), 0, a.stream, a.d_bases, ws.sorted, ws.bucket_off, ws.sub_off, pl.nb, ws.totals, partial, sh.sub, rs);
+  launch_accum<F>(a.stream, a.d_bases, ws.sorted, ws.bucket_off, ws.sub_off, pl.nb, ws.totals, partial, sh.sub, sh.max_subs, rs, G);
   VZ_EV(4);
   launch_combine<F>(a.stream, partial, ws.sub_off, pl.nb, ws.heavy, ws.heavy_scratch, sh.lane_bits, sh.heavy_min, ws.heavy_done, rs, G);
   VZ_EV(5);      // (stage 2 of the very heavy buckets: the last of a bucket's workgroups, inside k_combine)
@@ -1179,7 +1195,7 @@ static hipError_t msm_launch_impl(hipStream_t stream, MsmWorkspace& ws, const ui
   const MsmCall a{stream, ws, d_bases, d_scalars, n, scalars_mont, msm_tuning().signed_scalars, split_ones, reinterpret_cast<uint32_t*>(pinned_dst), ev, tb, rg};
   switch (sh.path) {
     case MSM_PATH_FIXED: return launch_fixed<C>(a, sh);
-    case MSM_PATH_SMALL: return launch_small<C>(a, sh);
+    case MSM_PATH_SMALL: return launch_small<C>(a, sh, msm_small_sum_kernel());
     default: return launch_large<C>(a, sh);
   }
 }
