@@ -489,6 +489,24 @@ int vimz_cf_state_chain(vimz_cf* v, const uint64_t* z_start, const uint64_t* ste
 size_t vimz_cf_digest_stride(const vimz_cf* v);
 int vimz_cf_row_digests(vimz_cf* v, const uint64_t* step_inputs, size_t nsteps, uint64_t* digests_out);
 int vimz_cf_chain_from_digests(vimz_cf* v, const uint64_t* z_start, const uint64_t* step_inputs, const uint64_t* digests, size_t nsteps, uint64_t* zs_out);
+/* CompressedSNARK for the Nova + CycleFold proofs (vimz_amd/csrc/spartan.hip; framing of the blobs: vimz_amd/csrc/cf_compressed_parse.hpp): a few
+ * kilobytes a third party checks with the verifier key alone — any vimz_cf created for the same step circuit and commitment keys, whose folding
+ * state is neither read nor changed.  Needs ck_main of at least next_pow2(max(wires, constraints)) of F + F' and ck_cyclefold of as many for the
+ * CycleFold circuit (shorter: VIMZ_ERR_INVALID).  seconds (optional) = {set-up (first call on this object only), prove}.
+ * One chain: the statement of vimz_cf_verify, with an argument in place of every witness check — U_n (relaxed), u_n (strict) over F + F' on BN254 G1,
+ * cfU_n (relaxed, 7 public elements) over the CycleFold circuit on Grumpkin; carries (steps, z_0, z_n).  An object with no steps is refused.
+ * result: 0 = accepted; bit 0 / 1 the hash x0 / x1 that u_n carries; bit 2 / 3 / 4 the argument for U_n / cfU_n / u_n; bit 12 statement (steps, z0)
+ * differs; bit 13 malformed (a blob of another kind included). */
+size_t vimz_cf_compressed_size(vimz_cf* v);
+int vimz_cf_compress(vimz_cf* v, uint8_t* blob, size_t cap, double seconds[2]);
+int vimz_cf_verify_compressed(vimz_cf* vk, const uint8_t* blob, size_t len, uint64_t num_steps, const uint64_t* z0, uint32_t* result);
+/* Merged: the records (vimz_cf_merged_records) and one argument each for the folded main and the folded CycleFold instance.  The verifier replays the
+ * records as vimz_cf_merged_verify does and verifies the arguments for the instances IT computed.  A broken or orphaned object is refused.
+ * result: 0 = accepted; bit 0 / 1 a segment's main / CycleFold hash; bit 2 / 3 the argument for the folded main / CycleFold instance; bit 12 statement
+ * (steps, z0, adjacency); bit 13 malformed. */
+size_t vimz_cf_merged_compressed_size(const vimz_cf_merged* m);
+int vimz_cf_merged_compress(vimz_cf_merged* m, uint8_t* blob, size_t cap, double seconds[2]);
+int vimz_cf_verify_merged_compressed(vimz_cf* vk, const uint8_t* blob, size_t len, uint64_t num_steps, const uint64_t* z0, uint32_t* result);
 /* (test hooks — vimz_cf_poke, the host-only self-checks — are declared in vimz_hip_testing.h and exist only in libvimz_hip_testing.so) */
 
 /* ---- the decider of the Nova + CycleFold path: `Decider::preprocess` / `Decider::prove` / `Decider::verify` of the Sonobe backend

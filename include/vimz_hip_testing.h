@@ -252,6 +252,15 @@ int64_t vimz_test_spartan_instance(vimz_ctx* ctx, int curve, size_t n_c, size_t 
 int vimz_test_spartan_instance_verify(vimz_ctx* ctx, int curve, size_t n_c, size_t n_w, const vimz_coo* A, const vimz_coo* B, const vimz_coo* C, const vimz_bases* ck,
                                       const uint64_t digest[4], uint32_t side_tag, const char* label, const uint64_t inst[28], int has_E, const uint64_t* words,
                                       size_t n_words);
+/* The same pair for an instance with n_pub >= 1 public elements at the LAST n_pub wires of Z (wire 0 stays u): 1 <= n_pub <= 8, n_w >= n_pub + 2 (at least one
+ * committed wire), anything else VIMZ_ERR_INVALID.  comm_W covers wires 1 .. n_w - 1 - n_pub (wire i over ck[i - 1]); inst = cW, cE (8 words each), u, then
+ * X[0 .. n_pub) (4 words each).  At n_pub = 2 every byte is the pair's above (tests/test_gpu_spartan_pub.py). */
+int64_t vimz_test_spartan_instance_pub(vimz_ctx* ctx, int curve, size_t n_c, size_t n_w, uint32_t n_pub, const vimz_coo* A, const vimz_coo* B, const vimz_coo* C,
+                                       const uint64_t* Z, const uint64_t* E, const vimz_bases* ck, const uint64_t digest[4], uint32_t side_tag, const char* label, void* buf,
+                                       size_t cap);
+int vimz_test_spartan_instance_pub_verify(vimz_ctx* ctx, int curve, size_t n_c, size_t n_w, uint32_t n_pub, const vimz_coo* A, const vimz_coo* B, const vimz_coo* C,
+                                          const vimz_bases* ck, const uint64_t digest[4], uint32_t side_tag, const char* label, const uint64_t* inst, int has_E,
+                                          const uint64_t* words, size_t n_words);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,7 @@
 """End-to-end run of one transformation on the GPU, the way `vimz -b nova-snark -f <t>` sequences it
 (vimz/src/nova_snark_backend/mod.rs:22-80): prepare input -> prepare folding (circuit + key) -> fold every row -> verify.
 Prints the span times the reference logs ("Prepare input", "Prepare folding", "Fold input", "Verify folded proof").
-usage: e2e.py <transformation> <resolution> [segments] [ivc|accumulator|cyclefold] [proof file prefix or -] [witness batch] [--ptau FILE [--verify-ptau]]
+usage: e2e.py <transformation> <resolution> [segments] [ivc|accumulator|cyclefold] [proof file prefix or -] [witness batch] [--ptau FILE [--verify-ptau]] [--compress]
 ivc (default): ONE proof object — the rows are proven as `segments` Nova IVCs of contiguous row segments folded concurrently and
 merged (vimz_ivc_merge), then compressed;
 accumulator: NIFS accumulators of the segments merged by a final fold;
@@ -10,7 +10,9 @@ cyclefold: the Sonobe backend's sequence (vimz/src/sonobe_backend/mod.rs:52-95: 
 CycleFold; with one segment also the decider (Prepare decider, Generate decider proof: vimz_decider_*; the full one, or VIMZ_E2E_DECIDER=light) and the calldata bytes.
 --ptau FILE (cyclefold only): the KZG SRS and the decider's key come from that powers-of-tau string (iden3.read_ptau, hip.kzg_from_powers, hip.Decider(powers=));
 --verify-ptau: the string is judged first (hip.verify_powers) and a refused one ends the run
-instead of a tau and a trapdoor drawn in this process."""
+instead of a tau and a trapdoor drawn in this process.
+--compress (cyclefold only): the proof — one chain or the merged segments — is compressed (vimz_cf_compress / vimz_cf_merged_compress), the blob verified on a
+second CycleFoldIVC that never folded and, with a proof file prefix, written to <prefix>.cfcompressed.bin (verify elsewhere: tools/verify_proof.py)."""
 import json
 import sys
 import time
@@ -26,6 +28,9 @@ from vimz_amd.distributed import fold_local_segments, fold_segments_merged  # no
 def main():
     powers = None
     verify_ptau = "--verify-ptau" in sys.argv
+    compress = "--compress" in sys.argv
+    if compress:
+        sys.argv.remove("--compress")
     if verify_ptau:
         sys.argv.remove("--verify-ptau")
     if "--ptau" in sys.argv:
@@ -59,6 +64,8 @@ def main():
     pmode = mode if mode in ("ivc", "cyclefold") else "accumulator"
     if powers is not None and mode != "cyclefold":
         sys.exit("e2e.py: --ptau goes with the cyclefold mode")
+    if compress and mode != "cyclefold":
+        sys.exit("e2e.py: --compress goes with the cyclefold mode (the ivc mode always compresses)")
     ctxs, circuit, params, made, setup_split = folding.prepare_folding_overlapped(0, S, t, res, mode=pmode, batch=batch, powers=powers, verify_powers=verify_ptau)
     batch = batch or folding.default_batch(circuit)
     th_in.join()
@@ -130,6 +137,22 @@ def main():
         ze = proof.state()[1] if S > 1 else proof.state()[0]
         if save and S > 1:
             proof.save().tofile(f"{save}.cfmerged.bin")       # verify elsewhere: tools/verify_proof.py
+        if compress:
+            blob, tc = proof.compress()
+            spans["Prepare compression"] = tc["setup_s"]
+            spans["Compress proof"] = tc["prove_s"]
+            vk2 = hip.CycleFoldIVC(ctxs[0], circuit, params.ck, ck2, max_batch=1)      # what a verifying process constructs
+            t0 = time.time()
+            try:
+                folding.verify_compressed_proof(vk2, blob, len(rows), z0)
+            except _lib.VimzError as e:
+                print(f"the compressed proof does not verify: {e}", file=sys.stderr)
+                ok = False
+            spans["Verify compressed proof"] = time.time() - t0
+            vk2.close()
+            compressed_bytes = int(len(blob))
+            if save:
+                blob.tofile(f"{save}.cfcompressed.bin")
         decider = None
         if S == 1:      # the reference's next spans (mod.rs:72-80): Decider::preprocess, Decider::prove, verify_final_proof -> the calldata (solidity.rs:13-27)
             from vimz_amd import calldata
@@ -154,7 +177,7 @@ def main():
                 open(f"{save}.calldata.bin", "wb").write(raw)
             dec.close()
         print(json.dumps({"config": f"{t}_step_{res}", "mode": "cyclefold", "steps": len(rows), "segments": S, "witness_batch": batch, "proof_objects": 1, "verified": ok, "spans_s": spans, "prepare_folding_split_s": setup_split,
-                          "state_chain_s": t_chain, "merge_s": t_merge, "info": cfs[0].info(), "decider": decider,
+                          "state_chain_s": t_chain, "merge_s": t_merge, "info": cfs[0].info(), "decider": decider, "compressed_proof_bytes": compressed_bytes if compress else None,
                           "ms_per_step_first_segment": {k: 1e3 * sec / max(1, cfs[0].info()["steps"]) for k, (sec, n) in cfs[0].profile().items()},
                           "steps_per_s": len(rows) / spans["Fold input"], "total_s": sum(spans.values()), "wall_total_s": time.time() - t_wall, "final_state": [hex(z) for z in ze]}))
         return

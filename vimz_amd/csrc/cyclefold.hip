@@ -315,6 +315,7 @@ extern "C" {
 void vimz_cf_free(vimz_cf* v) {
   if (!v) return;
   if (v->orphan_merged) v->orphan_merged(v);
+  if (v->spartan_free) v->spartan_free(v);
   if (v->pri) vimz_prover_free(v->pri);
   if (v->ctx) {
     std::lock_guard<std::mutex> g(v->ctx->mu);

@@ -44,6 +44,8 @@ struct vimz_cf {
   // merged proofs that use this prover as their verifier key: freeing it first orphans them (buffers released, later calls fail cleanly)
   std::vector<struct vimz_cf_merged*> merged_dependents;
   void (*orphan_merged)(vimz_cf*) = nullptr;
+  // transposed shapes and scratch of the compressed proof (spartan.hip: vimz_cf_compress / vimz_cf_verify_compressed and the merged pair), made on first use
+  void* spartan_cache = nullptr; void (*spartan_free)(vimz_cf*) = nullptr;
 };
 
 namespace {

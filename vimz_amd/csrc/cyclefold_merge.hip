@@ -1,6 +1,7 @@
 // ONE proof object out of several row segments' Nova + CycleFold proofs (vimz_cf_merge*): see the protocol comment below.  The prover itself:
 // cyclefold.hip.
-#include "cyclefold_internal.hpp"
+#include "cyclefold_merge_internal.hpp"
+#include "cf_compressed_parse.hpp"
 #include "decider_view.hpp"
 #ifdef VIMZ_TESTING
 #include "../../include/vimz_hip_testing.h"
@@ -22,27 +23,9 @@
 // A.z_end = B.z_start;  h = SHA3("vimz-cf-merge-node-v1" ‖ A.h ‖ B.h ‖ T_p ‖ T_q), r_p = chal(h ‖ 'p'), r_q = chal(h ‖ 'q');  both pairs of
 // relaxed accumulators fold with E += r·T + r²·E_B.  The verifier recomputes every run's accumulator from its records on its own.
 // Ours, like the circuits.
-struct CfSegRec { uint64_t n = 0; std::vector<Fe> zs, ze; CfMainRelaxed U; G1Aff UW, UE; CfMainFresh u; G1Aff uW; CfRelaxed cfU; G1Aff T1, T2; G2Aff Tc; };
-struct CfAcc { uint8_t h[32] = {}; uint64_t n = 0; std::vector<Fe> zs, ze; G1Aff cW, cE; Fe u, x0, x1; G2Aff qW, qE; Fq qu; Fq qx[CF_IO]; };
-struct CfJunction { G1Aff Tp; G2Aff Tq; };
-struct vimz_cf_merged {
-  vimz_cf* vk = nullptr;                  // shapes, keys, context: must outlive this object
-  std::vector<CfSegRec> segs;
-  // RUNS: segs[run_start[k] .. run_start[k+1]) were folded in row order by vimz_cf_merge on one GPU (one run per GPU of a sharded proof);
-  // run k > 0 was folded into the runs before it as a whole (vimz_cf_merge_merged: two relaxed accumulators), junction k-1 holds that fold's
-  // two cross-term commitments
-  std::vector<uint32_t> run_start{0};
-  std::vector<CfJunction> junctions;
-  CfAcc acc;
-  uint32_t* dev = nullptr;                // one allocation
-  uint32_t *Zp = nullptr, *Ep = nullptr, *AZp = nullptr, *BZp = nullptr, *CZp = nullptr, *Tp = nullptr;
-  uint32_t *Zq = nullptr, *Eq = nullptr, *AZq = nullptr, *BZq = nullptr, *CZq = nullptr, *Tq = nullptr;
-  bool broken = false;
-  double seconds[4] = {};                 // GPU cross terms + commitments, folds, host, total
-};
-
+// (the object itself: cyclefold_merge_internal.hpp)
 namespace {
-const uint64_t CF_MERGED_MAGIC = 0x32474d46435a56ull;      // "VZCFMG2"
+const uint64_t CF_MERGED_MAGIC = cfz::RECORDS_MAGIC;      // "VZCFMG2"
 template <class F> void cfm_fe(Sha3& h, const F& m) { const F c = F::from_mont(m); h.update(c.v, 32); }
 template <class F> void cfm_pt(Sha3& h, const Affine<F>& p) { cfm_fe(h, p.x); cfm_fe(h, p.y); }
 void cfm_chal(const uint8_t h[32], char tag, const uint8_t* extra, size_t n, uint32_t out[4]) {
@@ -384,6 +367,31 @@ int vimz_cf_merged_save(vimz_cf_merged* m, uint8_t* blob, size_t cap) {
   P_TRY(hipStreamSynchronize(s));
   return VIMZ_OK;
 }
+// the elements of framed records (w[*pos ..) holds S segments, then R − 1 junctions; the caller has checked the length): every element below its
+// modulus, every point on its curve
+static bool cfm_read_elements(const uint64_t* w, size_t* at, size_t lz, size_t S, size_t R, std::vector<CfSegRec>& segs, std::vector<CfJunction>& junctions) {
+  size_t pos = *at;
+  bool ok = true;
+  auto fe = [&](auto* dst) { typedef std::decay_t<decltype(*dst)> F; F c; memcpy(c.v, w + pos, 32); pos += 4; if (!c.is_reduced()) ok = false; *dst = F::to_mont(c); };
+  auto u256 = [&](U256w* dst) { memcpy(dst->w, w + pos, 32); pos += 4; Fq c; memcpy(c.v, dst->w, 32); if (!c.is_reduced()) ok = false; };
+  auto g1 = [&](G1Aff* P) { fe(&P->x); fe(&P->y); if (ok && !aff_on_curve(*P)) ok = false; };
+  auto g2 = [&](G2Aff* P) { fe(&P->x); fe(&P->y); if (ok && !aff_on_curve(*P)) ok = false; };
+  segs.assign(S, CfSegRec());
+  for (auto& sg : segs) {
+    sg.n = w[pos++];
+    sg.zs.resize(lz); sg.ze.resize(lz);
+    for (auto& z : sg.zs) fe(&z);
+    for (auto& z : sg.ze) fe(&z);
+    g1(&sg.UW); g1(&sg.UE); fe(&sg.U.u); fe(&sg.U.x0); fe(&sg.U.x1); sg.U.W = nn_point(sg.UW); sg.U.E = nn_point(sg.UE);
+    g1(&sg.uW); fe(&sg.u.x0); fe(&sg.u.x1); sg.u.W = nn_point(sg.uW);
+    g2(&sg.cfU.W); g2(&sg.cfU.E); fe(&sg.cfU.u); for (auto& e : sg.cfU.x) u256(&e);
+    g1(&sg.T1); g1(&sg.T2); g2(&sg.Tc);
+  }
+  junctions.assign(R - 1, CfJunction());
+  for (auto& j : junctions) { g1(&j.Tp); g2(&j.Tq); }
+  *at = pos;
+  return ok;
+}
 // parse and replay the records of an untrusted blob / ticket (w: 8-byte words) into m (vk set); *rec_words_out = their length
 static int cfm_parse_records(vimz_cf* vk, const uint64_t* w, size_t nwords, vimz_cf_merged* m, size_t* rec_words_out, const char* who) {
   vimz_ctx* ctx = vk->ctx; vimz_prover* p = vk->pri;
@@ -399,24 +407,7 @@ static int cfm_parse_records(vimz_cf* vk, const uint64_t* w, size_t nwords, vimz
   size_t pos = 8;
   for (uint64_t k = 0; k < R; k++) { if (w[pos] >= S || (k && w[pos] <= m->run_start.back())) return vz_fail(ctx, VIMZ_ERR_INVALID, "merged CycleFold proof: malformed runs"); m->run_start.push_back((uint32_t)w[pos++]); }
   if (m->run_start[0] != 0) return vz_fail(ctx, VIMZ_ERR_INVALID, "merged CycleFold proof: malformed runs");
-  bool ok = true;
-  auto fe = [&](auto* dst) { typedef std::decay_t<decltype(*dst)> F; F c; memcpy(c.v, w + pos, 32); pos += 4; if (!c.is_reduced()) ok = false; *dst = F::to_mont(c); };
-  auto u256 = [&](U256w* dst) { memcpy(dst->w, w + pos, 32); pos += 4; Fq c; memcpy(c.v, dst->w, 32); if (!c.is_reduced()) ok = false; };
-  auto g1 = [&](G1Aff* P) { fe(&P->x); fe(&P->y); if (ok && !aff_on_curve(*P)) ok = false; };
-  auto g2 = [&](G2Aff* P) { fe(&P->x); fe(&P->y); if (ok && !aff_on_curve(*P)) ok = false; };
-  m->segs.assign(S, CfSegRec());
-  for (auto& sg : m->segs) {
-    sg.n = w[pos++];
-    sg.zs.resize(lz); sg.ze.resize(lz);
-    for (auto& z : sg.zs) fe(&z);
-    for (auto& z : sg.ze) fe(&z);
-    g1(&sg.UW); g1(&sg.UE); fe(&sg.U.u); fe(&sg.U.x0); fe(&sg.U.x1); sg.U.W = nn_point(sg.UW); sg.U.E = nn_point(sg.UE);
-    g1(&sg.uW); fe(&sg.u.x0); fe(&sg.u.x1); sg.u.W = nn_point(sg.uW);
-    g2(&sg.cfU.W); g2(&sg.cfU.E); fe(&sg.cfU.u); for (auto& e : sg.cfU.x) u256(&e);
-    g1(&sg.T1); g1(&sg.T2); g2(&sg.Tc);
-  }
-  m->junctions.assign(R - 1, CfJunction());
-  for (auto& j : m->junctions) { g1(&j.Tp); g2(&j.Tq); }
+  const bool ok = cfm_read_elements(w, &pos, lz, (size_t)S, (size_t)R, m->segs, m->junctions);
   if (!ok || pos != rec_words) return vz_fail(ctx, VIMZ_ERR_INVALID, "merged CycleFold proof: an element of the records is not below its modulus, or a point is not on its curve");
   uint32_t fl = 0;
   if (!cfm_replay(vk, m->segs, m->run_start, m->junctions, m->acc, &fl)) return vz_fail(ctx, VIMZ_ERR_INVALID, "merged CycleFold proof: malformed records");
@@ -748,3 +739,24 @@ int vimz_cf_merged_kzg_open(vimz_cf_merged* m, int which, const uint64_t z[4], u
                     : vz_kzg_open_device(ctx, p->ck, 0, VIMZ_FIELD_BN254_FR, m->Ep, p->n_c, z, VIMZ_FORM_CANONICAL, eval_out, proof_xy);
 }
 }  // extern "C"
+
+// ---- what spartan.hip needs of this file for the compressed merged proof (cyclefold_merge_internal.hpp) ---------------------------------------
+namespace vz {
+std::vector<uint64_t> cf_merged_records_words(const vimz_cf_merged* m) {
+  const uint64_t shape[5] = {m->vk->pri->len_z, m->vk->pri->n_wires, m->vk->pri->n_c, m->vk->sec.n_w, m->vk->sec.n_c};
+  return cfm_records_words(shape, m->segs, m->run_start, m->junctions);
+}
+bool cf_merged_read_records(const vimz_cf* vk, const uint64_t* w, size_t nwords, std::vector<CfSegRec>& segs, std::vector<uint32_t>& run_start, std::vector<CfJunction>& junctions) {
+  const vimz_prover* p = vk->pri;
+  cfz::Shapes sh{}; sh.len_z = p->len_z; sh.n_w1 = p->n_wires; sh.n_c1 = p->n_c; sh.n_w2 = vk->sec.n_w; sh.n_c2 = vk->sec.n_c;
+  cfz::MergedFrame f;
+  if (!cfz::parse_records(w, nwords, sh, &f)) return false;
+  run_start.clear();
+  for (size_t k = 0; k < f.runs; k++) run_start.push_back((uint32_t)w[f.runs_at + k]);
+  size_t pos = f.segs_at;
+  return cfm_read_elements(w, &pos, p->len_z, f.segments, f.runs, segs, junctions) && pos == nwords;
+}
+bool cf_merged_replay(const vimz_cf* vk, const std::vector<CfSegRec>& segs, const std::vector<uint32_t>& run_start, const std::vector<CfJunction>& junctions, CfAcc& out, uint32_t* flags) {
+  return cfm_replay(vk, segs, run_start, junctions, out, flags);
+}
+}  // namespace vz

@@ -29,6 +29,8 @@
 #include "ec_mem.hpp"
 #include "proof_io.hpp"
 #include "merge_internal.hpp"
+#include "cyclefold_merge_internal.hpp"
+#include "cf_compressed_parse.hpp"
 #ifdef VIMZ_TESTING
 #include "../../include/vimz_hip_testing.h"
 #endif
@@ -155,19 +157,19 @@ template <class F>
 __global__ void __launch_bounds__(256) k_combine3(size_t n, const uint32_t* __restrict__ x, const uint32_t* __restrict__ y, const uint32_t* __restrict__ z, F r, F r2, uint32_t* __restrict__ out) {
   VZ_GRID_STRIDE(i, n) store_fe(out, i, F::add(load_fe<F>(x, i), F::add(F::mul(r, load_fe<F>(y, i)), F::mul(r2, load_fe<F>(z, i)))));
 }
-// out[0..N): the committed part of Z (public entries zeroed), zero-padded
+// out[0..N): the committed part of Z (public entries — wire 0 and the last n_pub wires — zeroed), zero-padded
 template <class F>
-__global__ void __launch_bounds__(256) k_committed_part(const uint32_t* __restrict__ Z, size_t nw, size_t N, uint32_t* __restrict__ out) {
-  VZ_GRID_STRIDE(i, N) store_fe(out, i, (i == 0 || i + 2 >= nw) ? F::zero() : load_fe<F>(Z, i));
+__global__ void __launch_bounds__(256) k_committed_part(const uint32_t* __restrict__ Z, size_t nw, size_t n_pub, size_t N, uint32_t* __restrict__ out) {
+  VZ_GRID_STRIDE(i, N) store_fe(out, i, (i == 0 || i + n_pub >= nw) ? F::zero() : load_fe<F>(Z, i));
 }
 
-// b of the W opening: eq(ry, ·) with the public slots (wire 0 = u, the last two wires = X0, X1) and the padding above the last wire
+// b of the W opening: eq(ry, ·) with the public slots (wire 0 = u, the last n_pub wires = X0, X1, ...) and the padding above the last wire
 // zeroed.  Those positions of the opened vector are NOT part of what comm_W may say about Z: their generators are live and honest
-// commitments never use them, so without the mask a prover could hide a correction of (u, X0, X1) there and prove the relation for
+// commitments never use them, so without the mask a prover could hide a correction of (u, X) there and prove the relation for
 // a z whose public entries differ from the instance's.
 template <class F>
-__global__ void __launch_bounds__(256) k_mask_public(uint32_t* __restrict__ b, size_t nw, size_t N) {
-  VZ_GRID_STRIDE(i, N) if (i == 0 || i + 2 >= nw) store_fe(b, i, F::zero());
+__global__ void __launch_bounds__(256) k_mask_public(uint32_t* __restrict__ b, size_t nw, size_t n_pub, size_t N) {
+  VZ_GRID_STRIDE(i, N) if (i == 0 || i + n_pub >= nw) store_fe(b, i, F::zero());
 }
 
 // ---- per-side resident data -----------------------------------------------------------------------------------------------------------
@@ -232,20 +234,22 @@ void spmv_any(hipStream_t s, const CsrDev& A, const CsrDev& B, const CsrDev& C, 
   if (n_long) hipLaunchKernelGGL(k_spmv_long<F>, dim3(spmv_long_blocks(n_long, n_med)), dim3(256), 0, s, A, B, C, dict, items, n_long, n_med, z, az, bz, cz);
 }
 
-void spartan_release(vimz_ivc* v) {
-  auto* c = (SpartanCache*)v->spartan_cache;
+void cache_release(vimz_ctx* ctx, void** slot) {
+  auto* c = (SpartanCache*)*slot;
   if (!c) return;
-  if (v->ctx) {
-    std::lock_guard<std::mutex> g(v->ctx->mu);
-    hipSetDevice(v->ctx->device);
-    hipStreamSynchronize(v->ctx->stream);
+  if (ctx) {
+    std::lock_guard<std::mutex> g(ctx->mu);
+    hipSetDevice(ctx->device);
+    hipStreamSynchronize(ctx->stream);
     for (void* d : c->owned) hipFree(d);
     for (auto& s : c->side) if (s.pin) hipHostFree(s.pin);
     c->ws.release();
   }
   delete c;
-  v->spartan_cache = nullptr;
+  *slot = nullptr;
 }
+void spartan_release(vimz_ivc* v) { cache_release(v->ctx, &v->spartan_cache); }
+void spartan_release_cf(vimz_cf* v) { cache_release(v->ctx, &v->spartan_cache); }
 
 // an independent generator for the inner-product term (nobody knows its discrete log with respect to the key)
 template <class C>
@@ -261,18 +265,18 @@ int derive_ipa_u(vimz_ctx* ctx, int curve, Affine<typename C::Base>* out) {
   return VIMZ_OK;
 }
 
-// CompressedSNARK::setup: transposed shapes and scratch on the device (caller does NOT hold the lock)
-int spartan_setup(vimz_ivc* v, SpartanCache** out) {
-  vimz_ctx* ctx = v->ctx;
-  if (v->spartan_cache) { *out = (SpartanCache*)v->spartan_cache; return VIMZ_OK; }
+// CompressedSNARK::setup: transposed shapes and scratch on the device (caller does NOT hold the lock).  Side 0: the prover's circuit over Fr with ck1,
+// side 1: `sec` over Fq with ck2 (the Nova IVC's secondary circuit, or the CycleFold circuit of a vimz_cf).
+int spartan_setup_sides(vimz_ctx* ctx, vimz_prover* p, const cb::Builder& b1, const SecDev& sec, const cb::BuilderT<Fq>& b2, const vimz_bases* ck1, const vimz_bases* ck2,
+                        void** slot, SpartanCache** out) {
+  if (*slot) { *out = (SpartanCache*)*slot; return VIMZ_OK; }
   std::unique_ptr<SpartanCache> c(new SpartanCache());
   int rc;
   if ((rc = derive_ipa_u<BnG1>(ctx, VIMZ_CURVE_BN254_G1, &c->ipa_u1))) return rc;
   if ((rc = derive_ipa_u<Grumpkin>(ctx, VIMZ_CURVE_GRUMPKIN, &c->ipa_u2))) return rc;
   std::lock_guard<std::mutex> g(ctx->mu);
   P_TRY(hipSetDevice(ctx->device));
-  vimz_prover* p = v->pri;
-  const cb::Builder& b1 = v->circ1->build->b; const cb::BuilderT<Fq>& b2 = v->c2.b;
+  struct FreeOnFail { SpartanCache* c; bool armed = true; ~FreeOnFail() { if (armed) { for (void* d : c->owned) hipFree(d); for (auto& s : c->side) if (s.pin) hipHostFree(s.pin); } } } guard{c.get()};
   for (int side = 0; side < 2; side++) {
     SideDev& S = c->side[side];
     if (side == 0) {
@@ -280,20 +284,30 @@ int spartan_setup(vimz_ivc* v, SpartanCache** out) {
       const cb::Csr* M3[3] = {&b1.A, &b1.B, &b1.C};
       P_TRY(build_transpose<Fe>(M3, S.n_c, S.n_w, S, c->owned));
     } else {
-      S.A = v->sec.A; S.B = v->sec.B; S.C = v->sec.C; S.dict = v->sec.dict; S.items = v->sec.long_items; S.n_long = v->sec.n_long; S.n_med = v->sec.n_med;
-      S.n_w = v->sec.n_w; S.n_c = v->sec.n_c;
+      S.A = sec.A; S.B = sec.B; S.C = sec.C; S.dict = sec.dict; S.items = sec.long_items; S.n_long = sec.n_long; S.n_med = sec.n_med;
+      S.n_w = sec.n_w; S.n_c = sec.n_c;
       const cb::Csr* M3[3] = {&b2.A, &b2.B, &b2.C};
       P_TRY(build_transpose<Fq>(M3, S.n_c, S.n_w, S, c->owned));
     }
     S.s = ceil_log2(S.n_c); S.t = ceil_log2(S.n_w); S.M = (size_t)1 << S.s; S.N = (size_t)1 << S.t;
     const size_t big = std::max(S.M, S.N);
-    if ((side == 0 ? v->ck1->n : v->ck2->n) < big) return vz_fail(ctx, VIMZ_ERR_INVALID, "compress: the commitment key is shorter than the padded shape (needs next_pow2(max(wires, constraints)) generators)");
+    if ((side == 0 ? ck1->n : ck2->n) < big) return vz_fail(ctx, VIMZ_ERR_INVALID, "compress: the commitment key is shorter than the padded shape (needs next_pow2(max(wires, constraints)) generators)");
     P_TRY(side_alloc(S, big, c->owned));
   }
+  guard.armed = false;
   *out = c.get();
-  v->spartan_cache = c.release();
-  v->spartan_free = spartan_release;
+  *slot = c.release();
   return VIMZ_OK;
+}
+int spartan_setup(vimz_ivc* v, SpartanCache** out) {
+  const int rc = spartan_setup_sides(v->ctx, v->pri, v->circ1->build->b, v->sec, v->c2.b, v->ck1, v->ck2, &v->spartan_cache, out);
+  if (!rc) v->spartan_free = spartan_release;
+  return rc;
+}
+int spartan_setup_cf(vimz_cf* v, SpartanCache** out) {
+  const int rc = spartan_setup_sides(v->ctx, v->pri, v->circ->build->b, v->sec, v->cf.b, v->ck1, v->ck2, &v->spartan_cache, out);
+  if (!rc) v->spartan_free = spartan_release_cf;
+  return rc;
 }
 
 template <class F>
@@ -315,16 +329,23 @@ F interp_quad(const F& s0, const F& s1, const F& s2, const F& r) {              
   return F::add(F::add(F::mul(l0, s0), F::mul(l1, s1)), F::mul(l2, s2));
 }
 
-// One relaxed instance of one side, as the prover and the verifier see it.
+// One relaxed instance of one side, as the prover and the verifier see it: n_pub >= 1 public elements X[0 .. n_pub) at the last n_pub wires of Z
+// (wire 0 = u).  The augmented circuits of the IVC and F' have two, a CycleFold instance CF_IO = 7.
+constexpr uint32_t MAX_PUB = 8;
 template <class F, class FS>
-struct Instance { Affine<FS> cW, cE; F u, X0, X1; bool has_E; };
+struct Instance { Affine<FS> cW, cE; F u, X[MAX_PUB]; uint32_t n_pub = 2; bool has_E; };
+template <class F, class FS>
+Instance<F, FS> instance2(const Affine<FS>& cW, const Affine<FS>& cE, const F& u, const F& X0, const F& X1, bool has_E) {
+  Instance<F, FS> I; I.cW = cW; I.cE = cE; I.u = u; I.X[0] = X0; I.X[1] = X1; I.n_pub = 2; I.has_E = has_E; return I;
+}
 
 template <class F, class FS>
 void absorb_instance(Transcript& tr, const F& digest, const Instance<F, FS>& I, uint32_t side_tag) {
   const uint64_t tag = side_tag; tr.absorb_words("side", &tag, 1);
   tr.absorb_fe("digest", digest);
   tr.absorb_fe("cWx", I.cW.x); tr.absorb_fe("cWy", I.cW.y); tr.absorb_fe("cEx", I.cE.x); tr.absorb_fe("cEy", I.cE.y);
-  tr.absorb_fe("u", I.u); tr.absorb_fe("X0", I.X0); tr.absorb_fe("X1", I.X1);
+  tr.absorb_fe("u", I.u);
+  for (uint32_t k = 0; k < I.n_pub; k++) { char tag[8]; snprintf(tag, sizeof(tag), "X%u", k); tr.absorb_fe(tag, I.X[k]); }      // ("X0", "X1" for the two of the IVC)
 }
 
 // ---- the bodies of the prover's loops (spartan_prove / ipa_prove and the test hooks of include/vimz_hip_testing.h run these very functions) --------
@@ -451,6 +472,7 @@ int spartan_prove(vimz_ctx* ctx, SpartanCache& cache, SideDev& S, hipStream_t s,
                   const Instance<F, typename C::Base>& I, const uint32_t* Z, const uint32_t* E, uint32_t side_tag, Transcript& tr, Writer& out, Fwd fwd,
                   bool forge_public_slot = false) {
   const size_t M = S.M, N = S.N, big = std::max(M, N);
+  if (I.n_pub < 1 || I.n_pub > MAX_PUB || S.n_w < I.n_pub + 2) return vz_fail(ctx, VIMZ_ERR_INVALID, "spartan: an instance needs 1..8 public elements and at least one committed wire");
   absorb_instance(tr, digest, I, side_tag);
   // vectors: (A,B,C)·Z padded to M, E padded to M
   P_TRY(hipMemsetAsync(S.va, 0, 32 * big, s)); P_TRY(hipMemsetAsync(S.vb, 0, 32 * big, s)); P_TRY(hipMemsetAsync(S.vc, 0, 32 * big, s)); P_TRY(hipMemsetAsync(S.ve, 0, 32 * big, s));
@@ -505,7 +527,7 @@ int spartan_prove(vimz_ctx* ctx, SpartanCache& cache, SideDev& S, hipStream_t s,
     }));
     len = half;
   }
-  // Z(ry) is what the bound vector holds; the committed part's evaluation is Z(ry) minus the three public entries' share
+  // Z(ry) is what the bound vector holds; the committed part's evaluation is Z(ry) minus the public entries' share
   F zr;
   P_TRY(hipMemcpyAsync(S.pin, S.vz, 32, hipMemcpyDeviceToHost, s));
   P_TRY(hipStreamSynchronize(s));
@@ -516,14 +538,16 @@ int spartan_prove(vimz_ctx* ctx, SpartanCache& cache, SideDev& S, hipStream_t s,
     for (size_t q = 0; q < k; q++) { const bool bit = (idx >> (k - 1 - q)) & 1; acc = F::mul(acc, bit ? pt[q] : F::sub(F::one(), pt[q])); }
     return acc;
   };
-  const F evalW = F::sub(zr, F::add(F::mul(I.u, eq_at(ry, 0)), F::add(F::mul(I.X0, eq_at(ry, S.n_w - 2)), F::mul(I.X1, eq_at(ry, S.n_w - 1)))));
+  F pub = F::mul(I.u, eq_at(ry, 0));
+  for (uint32_t k = 0; k < I.n_pub; k++) pub = F::add(pub, F::mul(I.X[k], eq_at(ry, S.n_w - I.n_pub + k)));
+  const F evalW = F::sub(zr, pub);
   out.fe(evalW);
   tr.absorb_fe("evalW", evalW);
   // opening of the committed part of Z at ry:  a = W' (into va), b = eq(ry, ·) (into vb), bases shifted by one wire
   int rc;
-  hipLaunchKernelGGL(k_committed_part<F>, dim3(stream_grid(N)), dim3(256), 0, s, Z, (size_t)S.n_w, N, S.va);
+  hipLaunchKernelGGL(k_committed_part<F>, dim3(stream_grid(N)), dim3(256), 0, s, Z, (size_t)S.n_w, (size_t)I.n_pub, N, S.va);
   P_TRY(eq_build<F>(s, S.vb, ry));
-  hipLaunchKernelGGL(k_mask_public<F>, dim3(stream_grid(N)), dim3(256), 0, s, S.vb, (size_t)S.n_w, N);
+  hipLaunchKernelGGL(k_mask_public<F>, dim3(stream_grid(N)), dim3(256), 0, s, S.vb, (size_t)S.n_w, (size_t)I.n_pub, N);
   if (forge_public_slot) {      // test hook (vimz_ivc_compress): the opened vector carries X0 − X0' = −1 in the slot of wire n−2
     const F m1 = F::neg(F::one());
     P_TRY(hipMemcpyAsync(S.va + 8 * (size_t)(S.n_w - 2), m1.v, 32, hipMemcpyHostToDevice, s)); P_TRY(hipStreamSynchronize(s));
@@ -600,6 +624,7 @@ bool ipa_verify(vimz_ctx* ctx, SpartanCache& cache, SideDev& S, hipStream_t s, T
 template <class F, class C, class B>
 bool spartan_verify(vimz_ctx* ctx, SpartanCache& cache, SideDev& S, hipStream_t s, const vimz_bases* ck, const Affine<typename C::Base>& Ugen, const F& digest,
                     const Instance<F, typename C::Base>& I, const B& shape /* host builder: A, B, C as CSR + dict */, uint32_t side_tag, Transcript& tr, Reader& in) {
+  if (I.n_pub < 1 || I.n_pub > MAX_PUB || S.n_w < I.n_pub + 2) return false;
   absorb_instance(tr, digest, I, side_tag);
   std::vector<F> tau(S.s);
   for (auto& x : tau) x = tr.challenge_fe<F>();
@@ -652,11 +677,12 @@ bool spartan_verify(vimz_ctx* ctx, SpartanCache& cache, SideDev& S, hipStream_t 
       vm = F::add(vm, F::mul(w[m], acc));
     }
   }
-  const F vz = F::add(evalW, F::add(F::mul(I.u, ey[0]), F::add(F::mul(I.X0, ey[S.n_w - 2]), F::mul(I.X1, ey[S.n_w - 1]))));
+  F vz = F::add(evalW, F::mul(I.u, ey[0]));
+  for (uint32_t k = 0; k < I.n_pub; k++) vz = F::add(vz, F::mul(I.X[k], ey[S.n_w - I.n_pub + k]));
   if (!F::mul(vm, vz).eq(claim)) return false;
   {   // the W opening is over the committed positions only: b = eq(ry, ·) with the public slots and the padding zeroed (k_mask_public)
     std::vector<F> eyW(ey);
-    for (size_t i = 0; i < eyW.size(); i++) if (i == 0 || i + 2 >= S.n_w) eyW[i] = F::zero();
+    for (size_t i = 0; i < eyW.size(); i++) if (i == 0 || i + I.n_pub >= S.n_w) eyW[i] = F::zero();
     if (!ipa_verify<F, C>(ctx, cache, S, s, tr, Ugen, ck, true, eyW, S.t, I.cW, evalW, in)) return false;
   }
   if (I.has_E && !ipa_verify<F, C>(ctx, cache, S, s, tr, Ugen, ck, false, ex, S.s, I.cE, cl[3], in)) return false;
@@ -678,11 +704,11 @@ void bind_statement(Transcript& tr, uint64_t steps, const std::vector<Fe>& z0, c
 
 template <class F> F u256_to_fe(const U256w& x) { return from_u256<F>(x); }
 
-Instance<Fe, Fq> inst_primary(const Loaded& L) { Instance<Fe, Fq> I; I.cW = L.U1.W; I.cE = L.U1.E; I.u = L.u1_run; I.X0 = u256_to_fe<Fe>(L.U1.X0); I.X1 = u256_to_fe<Fe>(L.U1.X1); I.has_E = true; return I; }
-Instance<Fq, Fe> inst_secondary(const Loaded& L) { Instance<Fq, Fe> I; I.cW = L.U2.W; I.cE = L.U2.E; I.u = L.u2_run; I.X0 = u256_to_fe<Fq>(L.U2.X0); I.X1 = u256_to_fe<Fq>(L.U2.X1); I.has_E = true; return I; }
+Instance<Fe, Fq> inst_primary(const Loaded& L) { return instance2<Fe, Fq>(L.U1.W, L.U1.E, L.u1_run, u256_to_fe<Fe>(L.U1.X0), u256_to_fe<Fe>(L.U1.X1), true); }
+Instance<Fq, Fe> inst_secondary(const Loaded& L) { return instance2<Fq, Fe>(L.U2.W, L.U2.E, L.u2_run, u256_to_fe<Fq>(L.U2.X0), u256_to_fe<Fq>(L.U2.X1), true); }
 Instance<Fq, Fe> inst_fresh(const Loaded& L) {
-  Instance<Fq, Fe> I; I.cW = L.u2.W; I.cE.x = Fe::zero(); I.cE.y = Fe::zero(); I.u = Fq::one();
-  I.X0 = cross_field<Fq>(L.u2.x0); I.X1 = cross_field<Fq>(L.u2.x1); I.has_E = false; return I;
+  G2Aff none; none.x = none.y = Fe::zero();
+  return instance2<Fq, Fe>(L.u2.W, none, Fq::one(), cross_field<Fq>(L.u2.x0), cross_field<Fq>(L.u2.x1), false);
 }
 
 }  // namespace
@@ -851,8 +877,8 @@ int vimz_ivc_merged_compress(vimz_ivc_merged* m, uint8_t* blob, size_t cap, doub
   write_records(m, out);
   Transcript tr("vimz-merged-compressed-v1");
   tr.absorb_words("records", out.w.data() + 2, out.w.size() - 2);
-  Instance<Fe, Fq> I1; I1.cW = m->acc.P.cW; I1.cE = m->acc.P.cE; I1.u = m->acc.P.u; I1.X0 = m->acc.P.X0; I1.X1 = m->acc.P.X1; I1.has_E = true;
-  Instance<Fq, Fe> I2; I2.cW = m->acc.Q.cW; I2.cE = m->acc.Q.cE; I2.u = m->acc.Q.u; I2.X0 = m->acc.Q.X0; I2.X1 = m->acc.Q.X1; I2.has_E = true;
+  const Instance<Fe, Fq> I1 = instance2<Fe, Fq>(m->acc.P.cW, m->acc.P.cE, m->acc.P.u, m->acc.P.X0, m->acc.P.X1, true);
+  const Instance<Fq, Fe> I2 = instance2<Fq, Fe>(m->acc.Q.cW, m->acc.Q.cE, m->acc.Q.u, m->acc.Q.X0, m->acc.Q.X1, true);
   auto fwd1 = [&](const uint32_t* z, uint32_t* az, uint32_t* bz, uint32_t* cz) { launch_spmv(p, s, z, az, bz, cz, 0); };
   auto fwd2 = [&](const uint32_t* z, uint32_t* az, uint32_t* bz, uint32_t* cz) { sec_spmv<Fq>(v->sec, s, z, az, bz, cz); };
   if ((rc = spartan_prove<Fe, BnG1>(ctx, *cache, cache->side[0], s, v->ck1, cache->ipa_u1, v->c1->digest, I1, m->Zp, m->Ep, 1, tr, out, fwd1))) return rc;
@@ -895,13 +921,238 @@ int vimz_ivc_verify_merged_compressed(vimz_ivc* v, const uint8_t* blob, size_t l
   hipStream_t s = ctx->stream;
   Transcript tr("vimz-merged-compressed-v1");
   tr.absorb_words("records", words.data() + 2, rw);
-  Instance<Fe, Fq> I1; I1.cW = R.P.cW; I1.cE = R.P.cE; I1.u = R.P.u; I1.X0 = R.P.X0; I1.X1 = R.P.X1; I1.has_E = true;
-  Instance<Fq, Fe> I2; I2.cW = R.Q.cW; I2.cE = R.Q.cE; I2.u = R.Q.u; I2.X0 = R.Q.X0; I2.X1 = R.Q.X1; I2.has_E = true;
+  const Instance<Fe, Fq> I1 = instance2<Fe, Fq>(R.P.cW, R.P.cE, R.P.u, R.P.X0, R.P.X1, true);
+  const Instance<Fq, Fe> I2 = instance2<Fq, Fe>(R.Q.cW, R.Q.cE, R.Q.u, R.Q.X0, R.Q.X1, true);
   const cb::Builder& b1 = v->circ1->build->b; const cb::BuilderT<Fq>& b2 = v->c2.b;
   bool ok1 = false, ok2 = false;
   try {
     ok1 = spartan_verify<Fe, BnG1>(ctx, *cache, cache->side[0], s, v->ck1, cache->ipa_u1, v->c1->digest, I1, b1, 1, tr, in);
     ok2 = ok1 && spartan_verify<Fq, Grumpkin>(ctx, *cache, cache->side[1], s, v->ck2, cache->ipa_u2, v->c2.digest, I2, b2, 2, tr, in);
+  } catch (const std::exception& e) { return vz_fail(ctx, VIMZ_ERR_INVALID, e.what()); }
+  if (!ok1) res |= 4;
+  if (ok1 && !ok2) res |= 8;
+  if (!in.ok || (ok2 && in.pos != in.n)) res |= 8192;
+  *result = res;
+  return VIMZ_OK;
+}
+
+
+// ---- CompressedSNARK for the Nova + CycleFold proofs (cyclefold.hip, cyclefold_merge.hip) ---------------------------------------------------------
+// One chain: the statement of vimz_cf_verify with every "this witness satisfies this instance" replaced by an argument — U_n (relaxed, over F' on
+// BN254 G1), u_n (the last instance of F': strict, no E) and cfU_n (relaxed, CF_IO public elements, over the CycleFold circuit on Grumpkin).
+// Merged: the records and one argument for each of the two folded instances.  Framing of both blobs: cf_compressed_parse.hpp.
+}  // extern "C"
+namespace {
+cfz::Shapes cf_shapes(const vimz_cf* v) {
+  cfz::Shapes sh{};
+  sh.len_z = v->pri->len_z; sh.n_w1 = v->pri->n_wires; sh.n_c1 = v->pri->n_c; sh.n_w2 = v->sec.n_w; sh.n_c2 = v->sec.n_c;
+  sh.s1 = ceil_log2(sh.n_c1); sh.t1 = ceil_log2(sh.n_w1); sh.s2 = ceil_log2(sh.n_c2); sh.t2 = ceil_log2(sh.n_w2);
+  return sh;
+}
+struct CfLoaded { CfMainRelaxed U; G1Aff UW, UE; CfMainFresh u; G1Aff uW; CfRelaxed cfU; };
+Instance<Fe, Fq> cf_inst_running(const CfLoaded& L) { return instance2<Fe, Fq>(L.UW, L.UE, L.U.u, L.U.x0, L.U.x1, true); }
+Instance<Fe, Fq> cf_inst_fresh(const CfLoaded& L) { return instance2<Fe, Fq>(L.uW, g1_identity(), Fe::one(), L.u.x0, L.u.x1, false); }
+Instance<Fq, Fe> cf_inst_cyclefold(const G2Aff& cW, const G2Aff& cE, const Fq& u, const Fq* x) {
+  static_assert(CF_IO <= (int)MAX_PUB, "a CycleFold instance's public elements must fit an Instance");
+  Instance<Fq, Fe> I; I.cW = cW; I.cE = cE; I.u = u; I.n_pub = CF_IO; I.has_E = true;
+  for (int k = 0; k < CF_IO; k++) I.X[k] = x[k];
+  return I;
+}
+Instance<Fq, Fe> cf_inst_cyclefold(const CfLoaded& L) {
+  Fq x[CF_IO];
+  for (int k = 0; k < CF_IO; k++) x[k] = from_u256<Fq>(L.cfU.x[k]);
+  return cf_inst_cyclefold(L.cfU.W, L.cfU.E, cross_field<Fq>(L.cfU.u), x);      // u is a small integer: the same in both fields
+}
+}  // namespace
+extern "C" {
+
+size_t vimz_cf_compressed_size(vimz_cf* v) {
+  if (!v) return 0;
+  return 8 * cfz::chain_words(cf_shapes(v));
+}
+
+int vimz_cf_compress(vimz_cf* v, uint8_t* blob, size_t cap, double seconds[2]) {
+  if (!v || !blob) return VIMZ_ERR_INVALID;
+  vimz_ctx* ctx = v->ctx;
+  if (cap < vimz_cf_compressed_size(v)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_cf_compress: buffer too small");
+  if (v->broken) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_cf_compress: this IVC failed in the middle of a step");
+  if (v->i == 0) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_cf_compress: nothing has been folded");
+  double t0 = now_s();
+  SpartanCache* cache = nullptr;
+  int rc = spartan_setup_cf(v, &cache);
+  if (rc) return rc;
+  const double t_setup = now_s() - t0;
+  t0 = now_s();
+  std::lock_guard<std::mutex> g(ctx->mu);
+  P_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  P_TRY(hipStreamSynchronize(s));
+  vimz_prover* p = v->pri;
+  const cfz::Shapes sh = cf_shapes(v);
+  CfLoaded L; L.U = v->U; L.UW = v->UW; L.UE = v->UE; L.u = v->u; L.uW = v->uW; L.cfU = v->cfU;
+  Writer out;
+  out.word(cfz::CHAIN_MAGIC); out.word(v->i); out.word(p->len_z); out.word(sh.s1); out.word(sh.t1); out.word(sh.s2); out.word(sh.t2); out.word(0);
+  for (auto& z : v->z0) out.fe(z);
+  for (auto& z : p->z_cur) out.fe(z);
+  out.point(L.UW); out.point(L.UE); out.fe(L.U.u); out.fe(L.U.x0); out.fe(L.U.x1);
+  out.point(L.uW); out.fe(L.u.x0); out.fe(L.u.x1);
+  out.point(L.cfU.W); out.point(L.cfU.E); out.fe(L.cfU.u); for (auto& e : L.cfU.x) out.u256(e);
+  Transcript tr("vimz-cf-compressed-v1");
+  bind_statement(tr, v->i, v->z0, p->z_cur);
+  tr.absorb_words("inst", out.w.data() + 8 + 8 * p->len_z, cfz::CHAIN_INSTANCE_WORDS);
+  auto fwd1 = [&](const uint32_t* z, uint32_t* az, uint32_t* bz, uint32_t* cz) { launch_spmv(p, s, z, az, bz, cz, 0); };
+  auto fwd2 = [&](const uint32_t* z, uint32_t* az, uint32_t* bz, uint32_t* cz) { sec_spmv<Fq>(v->sec, s, z, az, bz, cz); };
+  const Fq cf_digest = cross_field<Fq>(v->c1->digest);      // (SHA3 of BOTH shapes, 250 bits: the same integer in either field)
+  if ((rc = spartan_prove<Fe, BnG1>(ctx, *cache, cache->side[0], s, v->ck1, cache->ipa_u1, v->c1->digest, cf_inst_running(L), p->Zrun, p->E, 1, tr, out, fwd1))) return rc;
+  if ((rc = spartan_prove<Fe, BnG1>(ctx, *cache, cache->side[0], s, v->ck1, cache->ipa_u1, v->c1->digest, cf_inst_fresh(L), v->Zl, nullptr, 3, tr, out, fwd1))) return rc;
+  if ((rc = spartan_prove<Fq, Grumpkin>(ctx, *cache, cache->side[1], s, v->ck2, cache->ipa_u2, cf_digest, cf_inst_cyclefold(L), v->sec.Zrun, v->sec.E, 2, tr, out, fwd2))) return rc;
+  if (8 * out.w.size() != vimz_cf_compressed_size(v)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_cf_compress: internal size mismatch");
+  memcpy(blob, out.w.data(), 8 * out.w.size());
+  if (seconds) { seconds[0] = t_setup; seconds[1] = now_s() - t0; }
+  return VIMZ_OK;
+}
+
+// verify(vk, num_steps, z0).  `vk`: any vimz_cf created for the same step circuit and commitment keys (its folding state is neither read nor changed).
+// result: 0 = accepted; bit 0 / 1 the hash x0 / x1 carried by u_n; bit 2 / 3 / 4 the argument for U_n / cfU_n / u_n; bit 12 the statement (steps, z0)
+// differs; bit 13 malformed proof (also: a blob of another kind).
+int vimz_cf_verify_compressed(vimz_cf* v, const uint8_t* blob, size_t len, uint64_t num_steps, const uint64_t* z0, uint32_t* result) {
+  if (!v || !blob || !z0 || !result) return VIMZ_ERR_INVALID;
+  vimz_ctx* ctx = v->ctx;
+  SpartanCache* cache = nullptr;
+  int rc = spartan_setup_cf(v, &cache);
+  if (rc) return rc;
+  if (len & 7) { *result = 8192; return VIMZ_OK; }
+  std::vector<uint64_t> words(len / 8); if (len) memcpy(words.data(), blob, len);
+  const cfz::Shapes sh = cf_shapes(v);
+  cfz::ChainFrame fr;
+  if (!cfz::parse_chain(words.data(), words.size(), sh, &fr)) { *result = 8192; return VIMZ_OK; }
+  Reader in{words.data(), words.size()};
+  in.pos = fr.z0_at;
+  vimz_prover* p = v->pri;
+  const size_t lz = p->len_z;
+  const uint64_t steps = fr.steps;
+  uint32_t res = 0;
+  std::vector<Fe> z0p(lz), zn(lz), z0c(lz);
+  for (auto& z : z0p) z = in.fe<Fe>();
+  for (auto& z : zn) z = in.fe<Fe>();
+  for (uint32_t k = 0; k < lz; k++) { Fe c; memcpy(c.v, z0 + 4 * k, 32); if (!c.is_reduced()) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_cf_verify_compressed: z0 element not below the modulus"); z0c[k] = Fe::to_mont(c); }
+  if (steps != num_steps || steps == 0) res |= 4096;
+  for (uint32_t k = 0; k < lz; k++) if (!z0c[k].eq(z0p[k])) res |= 4096;
+  CfLoaded L;
+  L.UW = in.point<Fq>(); L.UE = in.point<Fq>(); L.U.u = in.fe<Fe>(); L.U.x0 = in.fe<Fe>(); L.U.x1 = in.fe<Fe>();
+  L.uW = in.point<Fq>(); L.u.x0 = in.fe<Fe>(); L.u.x1 = in.fe<Fe>();
+  L.cfU.W = in.point<Fe>(); L.cfU.E = in.point<Fe>(); L.cfU.u = in.fe<Fe>();
+  for (auto& e : L.cfU.x) { e = in.u256(); Fq c; memcpy(c.v, e.w, 32); if (!c.is_reduced()) in.ok = false; }
+  if (!in.ok || in.pos != fr.args_at) { *result = 8192; return VIMZ_OK; }
+  L.U.W = nn_point(L.UW); L.U.E = nn_point(L.UE); L.u.W = nn_point(L.uW);
+  // the two hashes u_n carries, recomputed from the verifier's own digest and the CLAIMED z0
+  if (!cf_hash_main(v->c1->digest, steps, z0c, zn.data(), L.U).eq(L.u.x0)) res |= 1;
+  if (!cf_hash_cf(v->c1->digest, L.cfU).eq(L.u.x1)) res |= 2;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  P_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  Transcript tr("vimz-cf-compressed-v1");
+  bind_statement(tr, steps, z0p, zn);
+  tr.absorb_words("inst", words.data() + fr.inst_at, cfz::CHAIN_INSTANCE_WORDS);
+  const cb::Builder& b1 = v->circ->build->b; const cb::BuilderT<Fq>& b2 = v->cf.b;
+  const Fq cf_digest = cross_field<Fq>(v->c1->digest);
+  bool ok1 = false, ok3 = false, ok2 = false;
+  try {
+    ok1 = spartan_verify<Fe, BnG1>(ctx, *cache, cache->side[0], s, v->ck1, cache->ipa_u1, v->c1->digest, cf_inst_running(L), b1, 1, tr, in);
+    ok3 = ok1 && spartan_verify<Fe, BnG1>(ctx, *cache, cache->side[0], s, v->ck1, cache->ipa_u1, v->c1->digest, cf_inst_fresh(L), b1, 3, tr, in);
+    ok2 = ok3 && spartan_verify<Fq, Grumpkin>(ctx, *cache, cache->side[1], s, v->ck2, cache->ipa_u2, cf_digest, cf_inst_cyclefold(L), b2, 2, tr, in);
+  } catch (const std::exception& e) { return vz_fail(ctx, VIMZ_ERR_INVALID, e.what()); }
+  if (!ok1) res |= 4;
+  if (ok1 && !ok3) res |= 16;
+  if (ok1 && ok3 && !ok2) res |= 8;
+  if (!in.ok || (ok2 && in.pos != in.n)) res |= 8192;
+  *result = res;
+  return VIMZ_OK;
+}
+
+size_t vimz_cf_merged_compressed_size(const vimz_cf_merged* m) {
+  if (!m || !m->vk) return 0;
+  const cfz::Shapes sh = cf_shapes(m->vk);
+  return 8 * (2 + cfz::records_words(sh, m->segs.size(), m->run_start.size()) + cfz::arg_words(sh.s1, sh.t1, true) + cfz::arg_words(sh.s2, sh.t2, true));
+}
+
+int vimz_cf_merged_compress(vimz_cf_merged* m, uint8_t* blob, size_t cap, double seconds[2]) {
+  if (!m || !blob) return VIMZ_ERR_INVALID;
+  if (!m->vk || !m->dev) return vz_fail(nullptr, VIMZ_ERR_INVALID, "vimz_cf_merged_compress: the prover this object was made with has been freed");
+  vimz_cf* v = m->vk; vimz_ctx* ctx = v->ctx;
+  if (m->broken || m->segs.empty()) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_cf_merged_compress: this object failed in the middle of a merge");
+  if (cap < vimz_cf_merged_compressed_size(m)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_cf_merged_compress: buffer too small");
+  double t0 = now_s();
+  SpartanCache* cache = nullptr;
+  int rc = spartan_setup_cf(v, &cache);
+  if (rc) return rc;
+  const double t_setup = now_s() - t0;
+  t0 = now_s();
+  std::lock_guard<std::mutex> g(ctx->mu);
+  P_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  P_TRY(hipStreamSynchronize(s));
+  vimz_prover* p = v->pri;
+  const std::vector<uint64_t> rec = vz::cf_merged_records_words(m);
+  Writer out;
+  out.word(cfz::MERGED_MAGIC); out.word(rec.size());
+  out.w.insert(out.w.end(), rec.begin(), rec.end());
+  Transcript tr("vimz-cf-merged-compressed-v1");
+  tr.absorb_words("records", out.w.data() + 2, out.w.size() - 2);
+  const Instance<Fe, Fq> I1 = instance2<Fe, Fq>(m->acc.cW, m->acc.cE, m->acc.u, m->acc.x0, m->acc.x1, true);
+  const Instance<Fq, Fe> I2 = cf_inst_cyclefold(m->acc.qW, m->acc.qE, m->acc.qu, m->acc.qx);
+  auto fwd1 = [&](const uint32_t* z, uint32_t* az, uint32_t* bz, uint32_t* cz) { launch_spmv(p, s, z, az, bz, cz, 0); };
+  auto fwd2 = [&](const uint32_t* z, uint32_t* az, uint32_t* bz, uint32_t* cz) { sec_spmv<Fq>(v->sec, s, z, az, bz, cz); };
+  if ((rc = spartan_prove<Fe, BnG1>(ctx, *cache, cache->side[0], s, v->ck1, cache->ipa_u1, v->c1->digest, I1, m->Zp, m->Ep, 1, tr, out, fwd1))) return rc;
+  if ((rc = spartan_prove<Fq, Grumpkin>(ctx, *cache, cache->side[1], s, v->ck2, cache->ipa_u2, cross_field<Fq>(v->c1->digest), I2, m->Zq, m->Eq, 2, tr, out, fwd2))) return rc;
+  if (8 * out.w.size() != vimz_cf_merged_compressed_size(m)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_cf_merged_compress: internal size mismatch");
+  memcpy(blob, out.w.data(), 8 * out.w.size());
+  if (seconds) { seconds[0] = t_setup; seconds[1] = now_s() - t0; }
+  return VIMZ_OK;
+}
+
+// verify(vk, num_steps, z0) of a compressed merged Nova + CycleFold proof.  result: 0 = accepted; bit 0 / 1 a segment's main / CycleFold hash; bit 2 / 3
+// the argument for the folded main / CycleFold instance; bit 12 statement (steps, z0, adjacency); bit 13 malformed (also: a blob of another kind).
+int vimz_cf_verify_merged_compressed(vimz_cf* v, const uint8_t* blob, size_t len, uint64_t num_steps, const uint64_t* z0, uint32_t* result) {
+  if (!v || !blob || !z0 || !result) return VIMZ_ERR_INVALID;
+  vimz_ctx* ctx = v->ctx;
+  SpartanCache* cache = nullptr;
+  int rc = spartan_setup_cf(v, &cache);
+  if (rc) return rc;
+  if (len & 7) { *result = 8192; return VIMZ_OK; }
+  std::vector<uint64_t> words(len / 8); if (len) memcpy(words.data(), blob, len);
+  const cfz::Shapes sh = cf_shapes(v);
+  cfz::MergedFrame fr;
+  if (!cfz::parse_merged(words.data(), words.size(), sh, &fr)) { *result = 8192; return VIMZ_OK; }
+  std::vector<CfSegRec> segs; std::vector<uint32_t> run_start; std::vector<CfJunction> junctions;
+  if (!vz::cf_merged_read_records(v, words.data() + fr.rec_at, fr.rec_words, segs, run_start, junctions)) { *result = 8192; return VIMZ_OK; }
+  uint32_t res = 0, fl = 0;
+  CfAcc R;
+  if (!vz::cf_merged_replay(v, segs, run_start, junctions, R, &fl)) { *result = 8192; return VIMZ_OK; }
+  if (fl & 1) res |= 1;
+  if (fl & 2) res |= 2;
+  if (fl & 4) res |= 4096;
+  vimz_prover* p = v->pri;
+  if (R.n != num_steps) res |= 4096;
+  for (uint32_t k = 0; k < p->len_z; k++) {
+    Fe c; memcpy(c.v, z0 + 4 * k, 32);
+    if (!c.is_reduced()) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_cf_verify_merged_compressed: z0 element not below the modulus");
+    if (!Fe::to_mont(c).eq(R.zs[k])) res |= 4096;
+  }
+  std::lock_guard<std::mutex> g(ctx->mu);
+  P_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  Transcript tr("vimz-cf-merged-compressed-v1");
+  tr.absorb_words("records", words.data() + fr.rec_at, fr.rec_words);
+  const Instance<Fe, Fq> I1 = instance2<Fe, Fq>(R.cW, R.cE, R.u, R.x0, R.x1, true);
+  const Instance<Fq, Fe> I2 = cf_inst_cyclefold(R.qW, R.qE, R.qu, R.qx);
+  const cb::Builder& b1 = v->circ->build->b; const cb::BuilderT<Fq>& b2 = v->cf.b;
+  Reader in{words.data(), words.size()};
+  in.pos = fr.args_at;
+  bool ok1 = false, ok2 = false;
+  try {
+    ok1 = spartan_verify<Fe, BnG1>(ctx, *cache, cache->side[0], s, v->ck1, cache->ipa_u1, v->c1->digest, I1, b1, 1, tr, in);
+    ok2 = ok1 && spartan_verify<Fq, Grumpkin>(ctx, *cache, cache->side[1], s, v->ck2, cache->ipa_u2, cross_field<Fq>(v->c1->digest), I2, b2, 2, tr, in);
   } catch (const std::exception& e) { return vz_fail(ctx, VIMZ_ERR_INVALID, e.what()); }
   if (!ok1) res |= 4;
   if (ok1 && !ok2) res |= 8;
@@ -1100,7 +1351,7 @@ int test_side_build(vimz_ctx* ctx, const vimz_r1cs* R, const vimz_bases* ck, Tes
 
 template <class F, class C>
 int64_t test_instance(vimz_ctx* ctx, int curve, const vimz_r1cs* R, const uint64_t* Zc, const uint64_t* Ec, const vimz_bases* ck, const uint64_t digest[4],
-                      uint32_t side_tag, const char* label, void* buf, size_t cap) {
+                      uint32_t side_tag, const char* label, uint32_t n_pub, void* buf, size_t cap) {
   typedef typename C::Base FS;
   std::vector<F> Z, E, dg;
   if (!canon_in(Zc, R->ncols, Z) || (Ec && !canon_in(Ec, R->nrows, E)) || !canon_in(digest, 1, dg)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_instance: element not below the modulus");
@@ -1118,9 +1369,10 @@ int64_t test_instance(vimz_ctx* ctx, int curve, const vimz_r1cs* R, const uint64
   if (Ec) { P_TRY(hipMalloc((void**)&Ed, 32 * E.size())); T.cache.owned.push_back(Ed); P_TRY(vec_up(s, Ed, E)); }
   P_TRY(hipStreamSynchronize(s));
   Instance<F, FS> I;
-  I.u = Z[0]; I.X0 = Z[S.n_w - 2]; I.X1 = Z[S.n_w - 1]; I.has_E = Ec != nullptr;
+  I.u = Z[0]; I.n_pub = n_pub; I.has_E = Ec != nullptr;
+  for (uint32_t k = 0; k < n_pub; k++) I.X[k] = Z[S.n_w - n_pub + k];
   I.cE.x = I.cE.y = FS::zero();
-  P_TRY(msm_run<C>(s, T.cache.ws, ck->d, Zd + 8, (size_t)S.n_w - 3, 1, 0, &I.cW, nullptr, nullptr, 0, nullptr));          // wire i -> ck[i − 1], the committed wires 1 .. n_w − 3
+  P_TRY(msm_run<C>(s, T.cache.ws, ck->d, Zd + 8, (size_t)S.n_w - 1 - n_pub, 1, 0, &I.cW, nullptr, nullptr, 0, nullptr));          // wire i -> ck[i − 1], the committed wires 1 .. n_w − 1 − n_pub
   if (Ec) P_TRY(msm_run<C>(s, T.cache.ws, ck->d, Ed, (size_t)S.n_c, 1, 0, &I.cE, nullptr, nullptr, 0, nullptr));
   Transcript tr(label);
   Writer out;
@@ -1135,11 +1387,11 @@ int64_t test_instance(vimz_ctx* ctx, int curve, const vimz_r1cs* R, const uint64
 
 template <class F, class C>
 int test_instance_verify(vimz_ctx* ctx, int curve, const vimz_r1cs* R, const vimz_bases* ck, const uint64_t digest[4], uint32_t side_tag, const char* label,
-                         const uint64_t inst[28], int has_E, const uint64_t* words, size_t n_words) {
+                         const uint64_t* inst, uint32_t n_pub, int has_E, const uint64_t* words, size_t n_words) {
   typedef typename C::Base FS;
   std::vector<F> sc, dg;
   std::vector<Affine<FS>> pts;
-  if (!canon_in(inst + 16, 3, sc) || !canon_in(digest, 1, dg)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_instance_verify: element not below the modulus");
+  if (!canon_in(inst + 16, 1 + n_pub, sc) || !canon_in(digest, 1, dg)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_instance_verify: element not below the modulus");
   const int bad = points_in(inst, 2, pts);
   if (bad == 1) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_instance_verify: coordinate not below the modulus");
   if (bad == 2) return 0;          // (a commitment off the curve: rejected, as Reader::point rejects one inside a proof)
@@ -1152,7 +1404,8 @@ int test_instance_verify(vimz_ctx* ctx, int curve, const vimz_r1cs* R, const vim
   TestSide T; TestShape<F> H;
   if ((rc = test_side_build<F>(ctx, R, ck, T, H))) return rc;
   Instance<F, FS> I;
-  I.cW = pts[0]; I.cE = pts[1]; I.u = sc[0]; I.X0 = sc[1]; I.X1 = sc[2]; I.has_E = has_E != 0;
+  I.cW = pts[0]; I.cE = pts[1]; I.u = sc[0]; I.n_pub = n_pub; I.has_E = has_E != 0;
+  for (uint32_t k = 0; k < n_pub; k++) I.X[k] = sc[1 + k];
   Transcript tr(label);
   Reader in{words, n_words};
   bool ok = false;
@@ -1163,9 +1416,10 @@ int test_instance_verify(vimz_ctx* ctx, int curve, const vimz_r1cs* R, const vim
 }
 
 template <class Fn>
-int64_t instance_dispatch(vimz_ctx* ctx, int curve, size_t n_c, size_t n_w, const vimz_coo* A, const vimz_coo* B, const vimz_coo* C, const vimz_bases* ck, const char* who, Fn fn) {
+int64_t instance_dispatch(vimz_ctx* ctx, int curve, size_t n_c, size_t n_w, uint32_t n_pub, const vimz_coo* A, const vimz_coo* B, const vimz_coo* C, const vimz_bases* ck, const char* who, Fn fn) {
   if (curve != VIMZ_CURVE_BN254_G1 && curve != VIMZ_CURVE_GRUMPKIN) return vz_fail(ctx, VIMZ_ERR_INVALID, who);
-  if (n_c < 2 || n_w < 4 || n_c > ((size_t)1 << 21) || n_w > ((size_t)1 << 21) || ck->curve != curve) return vz_fail(ctx, VIMZ_ERR_INVALID, who);
+  if (n_pub < 1 || n_pub > MAX_PUB || n_w < (size_t)n_pub + 2) return vz_fail(ctx, VIMZ_ERR_INVALID, who);
+  if (n_c < 2 || n_c > ((size_t)1 << 21) || n_w > ((size_t)1 << 21) || ck->curve != curve) return vz_fail(ctx, VIMZ_ERR_INVALID, who);
   size_t big = 1; while (big < std::max(n_c, n_w)) big <<= 1;
   if (ck->n < big) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_instance: the commitment key is shorter than the padded shape");
   vimz_r1cs* R = nullptr;
@@ -1219,9 +1473,16 @@ int vimz_test_spartan_fold_bases(vimz_ctx* ctx, int curve, const uint64_t* point
 int64_t vimz_test_spartan_instance(vimz_ctx* ctx, int curve, size_t n_c, size_t n_w, const vimz_coo* A, const vimz_coo* B, const vimz_coo* C, const uint64_t* Z,
                                    const uint64_t* E, const vimz_bases* ck, const uint64_t digest[4], uint32_t side_tag, const char* label, void* buf, size_t cap) {
   if (!ctx || !A || !B || !C || !Z || !ck || !digest || !label) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_instance: bad argument");
-  return instance_dispatch(ctx, curve, n_c, n_w, A, B, C, ck, "vimz_test_spartan_instance: bad argument", [&](const vimz_r1cs* R) -> int64_t {
-    return curve == VIMZ_CURVE_BN254_G1 ? test_instance<Fe, BnG1>(ctx, curve, R, Z, E, ck, digest, side_tag, label, buf, cap)
-                                        : test_instance<Fq, Grumpkin>(ctx, curve, R, Z, E, ck, digest, side_tag, label, buf, cap);
+  return vimz_test_spartan_instance_pub(ctx, curve, n_c, n_w, 2, A, B, C, Z, E, ck, digest, side_tag, label, buf, cap);
+}
+
+int64_t vimz_test_spartan_instance_pub(vimz_ctx* ctx, int curve, size_t n_c, size_t n_w, uint32_t n_pub, const vimz_coo* A, const vimz_coo* B, const vimz_coo* C,
+                                       const uint64_t* Z, const uint64_t* E, const vimz_bases* ck, const uint64_t digest[4], uint32_t side_tag, const char* label, void* buf,
+                                       size_t cap) {
+  if (!ctx || !A || !B || !C || !Z || !ck || !digest || !label) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_instance: bad argument");
+  return instance_dispatch(ctx, curve, n_c, n_w, n_pub, A, B, C, ck, "vimz_test_spartan_instance: bad argument", [&](const vimz_r1cs* R) -> int64_t {
+    return curve == VIMZ_CURVE_BN254_G1 ? test_instance<Fe, BnG1>(ctx, curve, R, Z, E, ck, digest, side_tag, label, n_pub, buf, cap)
+                                        : test_instance<Fq, Grumpkin>(ctx, curve, R, Z, E, ck, digest, side_tag, label, n_pub, buf, cap);
   });
 }
 
@@ -1229,9 +1490,16 @@ int vimz_test_spartan_instance_verify(vimz_ctx* ctx, int curve, size_t n_c, size
                                       const uint64_t digest[4], uint32_t side_tag, const char* label, const uint64_t inst[28], int has_E, const uint64_t* words,
                                       size_t n_words) {
   if (!ctx || !A || !B || !C || !ck || !digest || !label || !inst || (!words && n_words)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_instance_verify: bad argument");
-  return (int)instance_dispatch(ctx, curve, n_c, n_w, A, B, C, ck, "vimz_test_spartan_instance_verify: bad argument", [&](const vimz_r1cs* R) -> int64_t {
-    return curve == VIMZ_CURVE_BN254_G1 ? test_instance_verify<Fe, BnG1>(ctx, curve, R, ck, digest, side_tag, label, inst, has_E, words, n_words)
-                                        : test_instance_verify<Fq, Grumpkin>(ctx, curve, R, ck, digest, side_tag, label, inst, has_E, words, n_words);
+  return vimz_test_spartan_instance_pub_verify(ctx, curve, n_c, n_w, 2, A, B, C, ck, digest, side_tag, label, inst, has_E, words, n_words);
+}
+
+int vimz_test_spartan_instance_pub_verify(vimz_ctx* ctx, int curve, size_t n_c, size_t n_w, uint32_t n_pub, const vimz_coo* A, const vimz_coo* B, const vimz_coo* C,
+                                          const vimz_bases* ck, const uint64_t digest[4], uint32_t side_tag, const char* label, const uint64_t* inst, int has_E,
+                                          const uint64_t* words, size_t n_words) {
+  if (!ctx || !A || !B || !C || !ck || !digest || !label || !inst || (!words && n_words)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_instance_verify: bad argument");
+  return (int)instance_dispatch(ctx, curve, n_c, n_w, n_pub, A, B, C, ck, "vimz_test_spartan_instance_verify: bad argument", [&](const vimz_r1cs* R) -> int64_t {
+    return curve == VIMZ_CURVE_BN254_G1 ? test_instance_verify<Fe, BnG1>(ctx, curve, R, ck, digest, side_tag, label, inst, n_pub, has_E, words, n_words)
+                                        : test_instance_verify<Fq, Grumpkin>(ctx, curve, R, ck, digest, side_tag, label, inst, n_pub, has_E, words, n_words);
   });
 }
 

@@ -353,26 +353,35 @@ def verify_folded_proof(proof, params, num_steps, initial_state):
         raise _lib.VimzError(_lib.ERR_UNSAT, f"Failed to verify folded proof (flags {r:#x})")
 
 
+COMPRESSED_MAGIC = {0x314E5343565A: "ivc", 0x31474D43565A: "merged", 0x314E534643565A: "cyclefold", 0x31474D4346565A: "cyclefold-merged"}
+
+
 def compress_proof(params, proof):
-    """CompressedSNARK::setup + prove (vimz/src/nova_snark_backend/mod.rs:52-59; spans "Prepare compression" / "Compress proof").
-    Returns (proof bytes, timings)."""
-    if proof.mode not in ("ivc", "merged"):
+    """CompressedSNARK::setup + prove (vimz/src/nova_snark_backend/mod.rs:52-59; spans "Prepare compression" / "Compress proof") for every proof
+    fold_input returns but the accumulator: the Nova IVC ("ivc"), its merged segments ("merged"), the Nova + CycleFold chain ("cyclefold":
+    vimz_cf_compress) and its merged segments ("cyclefold-merged": vimz_cf_merged_compress).  Returns (proof bytes, timings)."""
+    if proof.mode not in ("ivc", "merged", "cyclefold", "cyclefold-merged"):
         raise _lib.VimzError(_lib.ERR_INVALID, "Failed to compress proof: only a RecursiveSNARK (mode \"ivc\", or merged segments) can be compressed")
     return proof.prover.compress()
 
 
 def verify_compressed_proof(verifier_key, compressed, num_steps, initial_state):
     """compressed_proof.verify(&vk, num_steps, initial_state, secondary_initial_state) (mod.rs:63-67).  verifier_key: an IVC object
-    created for the same step circuit and keys (e.g. proof.prover, or a fresh hip.IVC in another process)."""
+    created for the same step circuit and keys (e.g. proof.prover, or a fresh hip.IVC in another process); for the two Nova + CycleFold
+    kinds a hip.CycleFoldIVC.  The blob's first word says which of the four kinds it is."""
     if isinstance(compressed, (bytes, bytearray, memoryview)):
         compressed = np.frombuffer(bytes(compressed), dtype=np.uint8)
     head = np.ascontiguousarray(compressed, dtype=np.uint8).reshape(-1)[:8]
     if head.size < 8:
         raise _lib.VimzError(_lib.ERR_INVALID, "Failed to verify proof: the blob is shorter than its header")
-    words = np.frombuffer(head.tobytes(), dtype=np.uint64)
-    if int(words[0]) == 0x31474D43565A:      # a compressed MERGED proof (vimz_ivc_merged_compress)
-        from .hip import MergedProof
+    from .hip import CycleFoldIVC, CycleFoldMerged, MergedProof
+    kind = COMPRESSED_MAGIC.get(int(np.frombuffer(head.tobytes(), dtype=np.uint64)[0]))
+    if kind is not None and kind.startswith("cyclefold") != isinstance(verifier_key, CycleFoldIVC):
+        raise _lib.VimzError(_lib.ERR_INVALID, f"Failed to verify proof: a compressed \"{kind}\" proof needs a {'CycleFoldIVC' if kind.startswith('cyclefold') else 'IVC'} as its verifier key")
+    if kind == "merged":      # a compressed MERGED proof (vimz_ivc_merged_compress)
         r = MergedProof.verify_compressed(verifier_key, compressed, num_steps, initial_state)
+    elif kind == "cyclefold-merged":
+        r = CycleFoldMerged.verify_compressed(verifier_key, compressed, num_steps, initial_state)
     else:
         r = verifier_key.verify_compressed(compressed, num_steps, initial_state)
     if r != 0:

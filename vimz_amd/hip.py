@@ -746,6 +746,28 @@ class CycleFoldIVC:
     def r1cs(self, side):
         return _r1cs_tables(self.ctx.lib.vimz_cf_export, self.h, side)
 
+    def compress(self):
+        """vimz_cf_compress: the succinct proof of this chain — arguments for U_n, u_n and cfU_n in place of their witnesses.
+        Returns (proof bytes as uint8 array, {"setup_s", "prove_s"})."""
+        lib = self.ctx.lib
+        lib.vimz_cf_compressed_size.argtypes = [C.c_void_p]
+        lib.vimz_cf_compressed_size.restype = C.c_size_t
+        lib.vimz_cf_compress.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double)]
+        n = lib.vimz_cf_compressed_size(self.h)
+        buf = np.zeros(n, dtype=np.uint8)
+        sec = (C.c_double * 2)()
+        self.ctx._chk(lib.vimz_cf_compress(self.h, _ptr(buf), n, sec))
+        return buf, {"setup_s": sec[0], "prove_s": sec[1]}
+
+    def verify_compressed(self, blob, num_steps, z0):
+        """vimz_cf_verify_compressed(vk, blob, num_steps, z0): 0 = accepted.  This object only supplies the verifier key."""
+        lib = self.ctx.lib
+        lib.vimz_cf_verify_compressed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint32)]
+        b = np.ascontiguousarray(blob, dtype=np.uint8)
+        r = C.c_uint32()
+        self.ctx._chk(lib.vimz_cf_verify_compressed(self.h, _ptr(b), b.size, int(num_steps), _ptr(_zlimbs(z0, self.circuit.len_z)), C.byref(r)))
+        return r.value
+
     def poke(self, which, index, value):
         """Test hook (vimz_cf_poke, include/vimz_hip_testing.h): exists only when the process runs on libvimz_hip_testing.so
         (VIMZ_HIP_LIBRARY=testing); the product library has no way to overwrite a prover's vectors."""
@@ -1606,6 +1628,29 @@ class CycleFoldMerged:
         self.ctx._chk(lib.vimz_cf_merged_kzg_open(self.h, which, _ptr(_zlimbs([z], 1)), _ptr(ev), _ptr(pr)))
         ints = lambda a: sum(int(a[k]) << (64 * k) for k in range(4))
         return ints(ev), (ints(pr[:4]), ints(pr[4:]))
+
+    def compress(self):
+        """vimz_cf_merged_compress: the records and one argument each for the folded main and CycleFold instance.
+        Returns (proof bytes as uint8 array, {"setup_s", "prove_s"})."""
+        lib = self.ctx.lib
+        lib.vimz_cf_merged_compressed_size.argtypes = [C.c_void_p]
+        lib.vimz_cf_merged_compressed_size.restype = C.c_size_t
+        lib.vimz_cf_merged_compress.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double)]
+        n = lib.vimz_cf_merged_compressed_size(self.h)
+        buf = np.zeros(n, dtype=np.uint8)
+        sec = (C.c_double * 2)()
+        self.ctx._chk(lib.vimz_cf_merged_compress(self.h, _ptr(buf), n, sec))
+        return buf, {"setup_s": sec[0], "prove_s": sec[1]}
+
+    @staticmethod
+    def verify_compressed(vk, blob, num_steps, z0):
+        """vimz_cf_verify_merged_compressed: 0 = accepted.  vk: a CycleFoldIVC for the same step circuit and keys (the verifier key only)."""
+        lib = vk.ctx.lib
+        lib.vimz_cf_verify_merged_compressed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint32)]
+        b = np.ascontiguousarray(blob, dtype=np.uint8)
+        r = C.c_uint32()
+        vk.ctx._chk(lib.vimz_cf_verify_merged_compressed(vk.h, _ptr(b), b.size, int(num_steps), _ptr(_zlimbs(z0, vk.circuit.len_z)), C.byref(r)))
+        return r.value
 
     def records(self):
         n = self.ctx.lib.vimz_cf_merged_records(self.h, None, 0)
