@@ -521,7 +521,8 @@ int vimz_cf_verify_merged_compressed(vimz_cf* vk, const uint8_t* blob, size_t le
  *      Grumpkin, non-natively over Fq; ≈ 2.75 M constraints on top of the step circuit's) and the LIGHT one (the opt-in `light-test` feature,
  *      vimz/Cargo.toml:56-59, vimz/Makefile:1-2, the contracts under contracts/light-test/: the CycleFold instance bound by its hash only).  Same public inputs, same
  *      25 words.  NTTs, the G1 / G2 multi-scalar multiplications, the final fold, the KZG openings and the keys' fixed-base multiplications run on
- *      the GPU; verification is host code (pairing.hpp).  The 25-word layout is the reference contracts' INTERFACE, not by itself a sound on-chain
+ *      the GPU; verification of ONE proof is host code (pairing.hpp), verification of MANY under one key (vimz_decider_verify_batch) runs its per-proof part —
+ *      point checks, scalar multiplications, Miller loops — on the GPU.  The 25-word layout is the reference contracts' INTERFACE, not by itself a sound on-chain
  *      decider: U_i's and u_i's commitments and the fold's r reach the contract as unconstrained calldata (aug/decider.hpp). ---------- */
 typedef struct vimz_decider vimz_decider;
 /* KZG::setup (inside `prepare_folding`, vimz/src/sonobe_backend/folding.rs:36-48): srs = [tau^i]G1 for i < n as a commitment key (use it as
@@ -746,6 +747,22 @@ int vimz_decider_verify(const vimz_decider* d, uint64_t steps, const uint64_t* z
 /* the same against a key given as words (vimz_decider_vk's layout): no context, no GPU */
 int vimz_decider_verify_key(const uint64_t* key_words, size_t n_key_words, uint64_t steps, const uint64_t* z0, const uint64_t* zi, uint32_t len_z,
                             const uint64_t words[100], uint32_t* result);
+/* MANY proofs under one key in one call — the receiving side of a decider proof: a contract's marketplace, an indexer that refuses bad calldata before it pays
+ * gas.  key_words: vimz_decider_vk's layout; steps: n; z0, zi: n·len_z elements; words: n·25 elements (4 little-endian limbs each).  results[i] is what
+ * vimz_decider_verify_key returns in *result for proof i alone, for every input: the same bits, its early returns included (malformed words give 16 and nothing
+ * else, a public element not below r gives 8 without the KZG bits, steps < 2 gives bit 1 and the checks go on).
+ * Proofs that pass the per-proof stage are cut into chunks of `chunk` (0: 256).  Under three 128-bit multipliers a proof from the OS, wiped after use on host
+ * and device, a chunk is accepted iff ONE product of Miller values is one after ONE final exponentiation (vimz_amd/csrc/decider_batch.hpp states it; wrong with
+ * probability about 2^-128); a refused chunk is judged member by member by the single verifier on the host's threads — no bisection: one bad proof costs its chunk
+ * `chunk` single verifications.  Every proof's B passes "on the twist" and r·B = O by itself before it enters a product.
+ * ctx != NULL: what grows with the batch runs on the GPU — the curve and subgroup flags of every point (k_powers_flags), twelve G1 scalar multiplications a proof
+ * and the per-chunk sums (k_g1_lincomb, k_col_runs), one Miller loop a proof (k_miller: homogeneous projective steps, sparse line products) —, the five
+ * fixed-G2 Miller loops and the final exponentiation of each chunk on the host.  ctx == NULL: every device stage is its host loop over the same per-thread
+ * functions on up to 16 threads — the path of a machine without a GPU.  n == 0 is VIMZ_OK.  A NULL pointer, an unparsable key or a len_z that is not the key's:
+ * VIMZ_ERR_INVALID with a message (vimz_last_error(ctx); of the calling thread when ctx is NULL).
+ * seconds (optional) = {parse + per-proof host work, per-proof device stage, Miller loops, host sums + fixed-G2 loops + final exponentiations, fallback, total} */
+int vimz_decider_verify_batch(vimz_ctx* ctx, const uint64_t* key_words, size_t n_key_words, uint32_t len_z, size_t n, const uint64_t* steps, const uint64_t* z0,
+                              const uint64_t* zi, const uint64_t* words, size_t chunk, uint32_t* results, double seconds[6]);
 
 /* ---- ONE proof object out of several row segments: the "host-side sequential final fold" of BASELINE.json's north_star for IVC proofs.
  *      fold_input returns ONE RecursiveSNARK (vimz/src/nova_snark_backend/folding.rs:27-43); row segments of an image folded

@@ -222,6 +222,19 @@ int vimz_test_decider_chains(vimz_ctx* ctx, int where, const uint64_t* gens_xy, 
 /* the full assignment z (canonical, 4 words per wire) of the decider circuit as vimz_decider_prove builds it for the proof `ivc` holds, check 5's chains from
  * the host (chains_on_gpu = 0) or from the device.  Returns the byte size (copies when buf is large enough); negative: vimz_decider_prove's error codes. */
 int64_t vimz_testing_decider_witness(vimz_decider* d, vimz_cf* ivc, int chains_on_gpu, void* buf, size_t cap);
+/* The two kernels of vimz_decider_verify_batch (vimz_amd/csrc/decider_batch.hip) on a caller's points, through the functions the product queues.
+ * _miller_loops: out[96·t ..] = the Miller value of (P_t, Q_t) over 6t + 2 with the two Frobenius steps (k_miller, pairing_stage.hpp's projective steps — NOT
+ * pairing.hpp's affine ones: the two differ by factors the final exponentiation removes; the word-for-word reference is tests/_miller_ref.py): the 12 Fq
+ * coefficients c0.c0.c0, c0.c0.c1, c0.c1.c0, .. c1.c2.c1, canonical, 8 words of 32 bits each; one when either point is the identity.  g1_xy: n >= 1 points of G1,
+ * 8 words of 64 bits each; g2_xy: n points of G2, 16 words (x.c0, x.c1, y.c0, y.c1); canonical, below q, the identity as zeros.
+ * _g1_lincomb: out_t = a_t + k_t·b_t (k_g1_lincomb) over exactly bits[t] <= 256 bits of k_t (4 words of 64 bits; the bits above are not read); points canonical, on
+ * the curve, the identity as zeros on both sides. */
+int vimz_test_miller_loops(vimz_ctx* ctx, const uint64_t* g1_xy, const uint64_t* g2_xy, size_t n, uint32_t* out);
+int vimz_test_g1_lincomb(vimz_ctx* ctx, const uint64_t* a_xy, const uint64_t* k, const uint32_t* bits, const uint64_t* b_xy, size_t n, uint64_t* out_xy);
+/* vimz_decider_verify_batch with GIVEN multipliers: 3n of 2 words (rho_i, sigma_i, sigma'_i of proof i; any non-zero 128-bit values, a zero is VIMZ_ERR_INVALID).
+ * Whoever knows the multipliers can make a chunk of wrong proofs pass: two proofs with their C points swapped pass under multipliers that are all one. */
+int vimz_testing_decider_verify_batch_scalars(vimz_ctx* ctx, const uint64_t* key_words, size_t n_key_words, uint32_t len_z, size_t n, const uint64_t* steps, const uint64_t* z0,
+                                              const uint64_t* zi, const uint64_t* words, size_t chunk, const uint64_t* multipliers, uint32_t* results, double seconds[6]);
 
 /* The compressed proof's kernels (vimz_amd/csrc/spartan.hip) on a caller's vectors, through the functions spartan_prove and ipa_prove run for every round
  * (tests/test_gpu_spartan_kernels.py).  field = VIMZ_FIELD_BN254_FR or _FQ, curve = VIMZ_CURVE_BN254_G1 or _GRUMPKIN (anything else: VIMZ_ERR_INVALID); elements are

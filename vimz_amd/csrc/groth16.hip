@@ -21,7 +21,7 @@
 #include "g16_powers.hpp"
 #include "g16_key_contrib.hpp"
 #include "g16_key_origin.hpp"
-#include "pairing.hpp"
+#include "decider_verify.hpp"
 #include "vecops_api.hpp"
 #ifdef VIMZ_TESTING
 #include "../../include/vimz_hip_testing.h"
@@ -809,79 +809,9 @@ int decider_setup_powers_impl(vimz_cf* v, bool light, const PowersString& S, con
 }
 
 // ---- the verifier: what contracts/*Verifier.sol::verifyNovaProof does with the 25 words (ContrastVerifier.sol:685-783) ---------------------------------
-struct VerifierKey {
-  Fe pp_hash; uint32_t len_z = 0;
-  G1Aff alpha; G2PAff beta, gamma, delta; std::vector<G1Aff> ic;
-  G1Aff kzg_g1; G2PAff kzg_g2, kzg_vk;
-};
-enum { DV_STEPS = 1, DV_KZG_W = 2, DV_KZG_E = 4, DV_GROTH16 = 8, DV_MALFORMED = 16 };
-G1Aff g1_lin(const G1Aff& a, const uint64_t* k256, const G1Aff& b) {      // a + k·b
-  G1 acc = aff_is_identity(a) ? G1::identity() : from_affine(a);
-  if (!aff_is_identity(b)) { G1 t = host_mul<Fq>(b, (const uint32_t*)k256, 256); add_full(acc, t); }
-  return to_affine(acc);
-}
-G1Aff g1_negate(const G1Aff& p) { G1Aff r = p; if (!aff_is_identity(p)) r.y = Fq::neg(p.y); return r; }
-// KZG10Verifier.check (:167-189): e(pi, VK) · e(x·(−pi) − c + y·G_1, G_2) == 1
-bool kzg_check(const VerifierKey& K, const G1Aff& c, const G1Aff& pi, const uint64_t* x, const uint64_t* y) {
-  G1 acc = host_mul<Fq>(g1_negate(pi), (const uint32_t*)x, 256);
-  { const G1Aff nc = g1_negate(c); if (!aff_is_identity(nc)) add_mixed(acc, nc); }
-  { G1 t = host_mul<Fq>(K.kzg_g1, (const uint32_t*)y, 256); add_full(acc, t); }
-  return vz::pairing::product_is_one({{pi, K.kzg_vk}, {to_affine(acc), K.kzg_g2}});
-}
-// words: the 25 calldata words as 4 little-endian limbs each.  Returns a bit set of DV_* (0 = accepted)
-uint32_t verify_words(const VerifierKey& K, uint64_t steps, const uint64_t* z0, const uint64_t* zi, const uint64_t* w) {
-  using namespace vz::pairing;
-  if (!consts().ok) return DV_MALFORMED;
-  uint32_t res = 0;
-  if (steps < 2) res |= DV_STEPS;                                                    // :697
-  G1Aff P[8]; static const int at[8] = {0, 2, 4, 6, 9, 15, 21, 23};              // U_i.cmW, U_i.cmE, u_i.cmW, cmT, A, C, proof_W, proof_E
-  for (int k = 0; k < 8; k++) if (!get_g1(w + 4 * at[k], &P[k]) || !g1_on_curve(P[k])) return res | DV_MALFORMED;
-  G2PAff B;      // calldata: x imaginary, x real, y imaginary, y real
-  if (!get_fq(w + 4 * 11, &B.x.c1) || !get_fq(w + 4 * 12, &B.x.c0) || !get_fq(w + 4 * 13, &B.y.c1) || !get_fq(w + 4 * 14, &B.y.c0) || !g2_on_curve(B) || !g2_in_subgroup(B)) return res | DV_MALFORMED;
-  Fe pub_el; std::vector<Fe> pub;
-  auto push_canon = [&](const uint64_t* c) { Fe x; memcpy(x.v, c, 32); if (!x.is_reduced()) return false; pub.push_back(Fe::to_mont(x)); return true; };      // checkField
-  pub.push_back(K.pp_hash); pub.push_back(cb::f_from_u64<Fe>(steps));
-  for (uint32_t k = 0; k < K.len_z; k++) if (!push_canon(z0 + 4 * k)) return res | DV_GROTH16;
-  for (uint32_t k = 0; k < K.len_z; k++) if (!push_canon(zi + 4 * k)) return res | DV_GROTH16;
-  const uint64_t* r = w + 4 * 8;
-  const G1Aff cmW = g1_lin(P[0], r, P[2]), cmE = g1_lin(P[1], r, P[3]);              // :712-713, :735-736
-  auto push_limbs = [&](const Fq& coord) { const Fq c = Fq::from_mont(coord); U256w u; memcpy(u.w, c.v, 32); uint64_t l[aug::DEC_LIMBS]; aug::decider_limbs55(u, l); for (int k = 0; k < aug::DEC_LIMBS; k++) pub.push_back(cb::f_from_u64<Fe>(l[k])); };
-  push_limbs(cmW.x); push_limbs(cmW.y); push_limbs(cmE.x); push_limbs(cmE.y);
-  for (int k = 17; k <= 20; k++) if (!push_canon(w + 4 * k)) res |= DV_GROTH16;
-  if (res & DV_GROTH16) return res;
-  push_limbs(P[3].x); push_limbs(P[3].y);
-  if (pub.size() + 1 != K.ic.size()) return res | DV_MALFORMED;
-  if (!kzg_check(K, cmW, P[6], w + 4 * 17, w + 4 * 19)) res |= DV_KZG_W;             // :725-730
-  if (!kzg_check(K, cmE, P[7], w + 4 * 18, w + 4 * 20)) res |= DV_KZG_E;             // :748-753
-  // Groth16 (:386-620): vk_x = IC_0 + Σ pub_k·IC_{k+1};  e(−A, B)·e(alpha, beta)·e(vk_x, gamma)·e(C, delta) == 1
-  G1 vkx = from_affine(K.ic[0]);
-  if (aff_is_identity(K.ic[0])) vkx = G1::identity();
-  for (size_t k = 0; k < pub.size(); k++) { if (pub[k].is_zero() || aff_is_identity(K.ic[k + 1])) continue; G1 t = host_mul_fr<Fq>(K.ic[k + 1], pub[k]); add_full(vkx, t); }
-  if (!product_is_one({{g1_negate(P[4]), B}, {K.alpha, K.beta}, {to_affine(vkx), K.gamma}, {P[5], K.delta}})) res |= DV_GROTH16;
-  return res;
-}
-// key blob (vimz_decider_vk): pp_hash, len_z, alpha (G1), beta, gamma, delta (G2: x.c0, x.c1, y.c0, y.c1), n_ic, IC points, KZG G_1 (G1), G_2, VK (G2)
-bool parse_key(const uint64_t* w, size_t n, VerifierKey* K) {
-  using namespace vz::pairing;
-  size_t pos = 0;
-  auto need = [&](size_t k) { return pos + k <= n; };
-  if (!need(5)) return false;
-  { Fe c; memcpy(c.v, w, 32); if (!c.is_reduced()) return false; K->pp_hash = Fe::to_mont(c); } pos += 4;
-  K->len_z = (uint32_t)w[pos++];
-  if (!need(8 + 48 + 1) || !get_g1(w + pos, &K->alpha)) return false; pos += 8;
-  for (G2PAff* p : {&K->beta, &K->gamma, &K->delta}) { if (!get_g2(w + pos, p)) return false; pos += 16; }
-  const uint64_t n_ic = w[pos++];
-  if (n_ic != 1 + (uint64_t)aug::decider_n_public(K->len_z) || !need(8 * n_ic + 8 + 32)) return false;
-  K->ic.resize(n_ic);
-  for (auto& p : K->ic) { if (!get_g1(w + pos, &p)) return false; pos += 8; }
-  if (!get_g1(w + pos, &K->kzg_g1)) return false; pos += 8;
-  if (!get_g2(w + pos, &K->kzg_g2) || !get_g2(w + pos + 16, &K->kzg_vk)) return false; pos += 32;
-  if (pos != n) return false;
-  if (!g1_on_curve(K->alpha) || !g1_on_curve(K->kzg_g1)) return false;
-  for (auto& p : K->ic) if (!g1_on_curve(p)) return false;
-  for (const G2PAff* p : {&K->beta, &K->gamma, &K->delta, &K->kzg_g2, &K->kzg_vk}) if (!g2_on_curve(*p) || !g2_in_subgroup(*p)) return false;
-  return true;
-}
+// (decider_verify.hpp: the verifier itself, shared with vimz_decider_verify_batch)
+using vz::dv::VerifierKey; using vz::dv::verify_words; using vz::dv::parse_key; using vz::dv::g1_negate;
+static_assert(vz::dv::LIMBS == aug::DEC_LIMBS && vz::dv::LIMB_BITS == aug::DEC_LIMB_BITS, "the verifier's limbs are the circuit's");
 VerifierKey key_of(const vimz_decider* d) {
   VerifierKey K; const G16Key& G = d->key;
   K.pp_hash = d->vk->c1->digest; K.len_z = d->circ.len_z;

@@ -7,6 +7,8 @@
 // step: this is a verifier that runs a handful of times a proof, not a hot loop) and the two Frobenius corrections; the final
 // exponentiation is a plain square-and-multiply by (q¹² − 1)/r — no cyclotomic tricks, no magic constants beyond the two moduli (the Frobenius
 // coefficients ξ^((q−1)/3), ξ^((q−1)/2) and the exponent are computed from them at first use).
+// The tower's Fq6 and Fq12 are host-and-device: the batched verifier's Miller kernel (pairing_stage.hpp, decider_batch.hip) runs on them with projective steps of
+// its own; miller_loop below stays the host's, word for word.
 // Checked in the CPU suite against the reference's own vectors: the six committed marketplace/proofs/*.proof verify through
 // vimz_decider_verify_key with the constants of contracts/*Verifier.sol (tests/test_decider_verify_host.py).
 #pragma once
@@ -60,22 +62,22 @@ inline Fq fq_u64(uint64_t v) { Fq c = Fq::zero(); c.v[0] = (uint32_t)v; c.v[1] =
 
 struct Fq6 {
   Fq2 c0, c1, c2;
-  static Fq6 zero() { Fq6 r; r.c0 = r.c1 = r.c2 = Fq2::zero(); return r; }
-  static Fq6 one() { Fq6 r = zero(); r.c0 = Fq2::one(); return r; }
-  bool is_zero() const { return c0.is_zero() && c1.is_zero() && c2.is_zero(); }
-  bool eq(const Fq6& b) const { return c0.eq(b.c0) && c1.eq(b.c1) && c2.eq(b.c2); }
-  static Fq6 add(const Fq6& a, const Fq6& b) { Fq6 r; r.c0 = Fq2::add(a.c0, b.c0); r.c1 = Fq2::add(a.c1, b.c1); r.c2 = Fq2::add(a.c2, b.c2); return r; }
-  static Fq6 sub(const Fq6& a, const Fq6& b) { Fq6 r; r.c0 = Fq2::sub(a.c0, b.c0); r.c1 = Fq2::sub(a.c1, b.c1); r.c2 = Fq2::sub(a.c2, b.c2); return r; }
-  static Fq6 neg(const Fq6& a) { return sub(zero(), a); }
-  static Fq6 mul(const Fq6& a, const Fq6& b) {      // schoolbook with v³ = ξ
+  static VZ_HD Fq6 zero() { Fq6 r; r.c0 = r.c1 = r.c2 = Fq2::zero(); return r; }
+  static VZ_HD Fq6 one() { Fq6 r = zero(); r.c0 = Fq2::one(); return r; }
+  VZ_HD bool is_zero() const { return c0.is_zero() && c1.is_zero() && c2.is_zero(); }
+  VZ_HD bool eq(const Fq6& b) const { return c0.eq(b.c0) && c1.eq(b.c1) && c2.eq(b.c2); }
+  static VZ_HD Fq6 add(const Fq6& a, const Fq6& b) { Fq6 r; r.c0 = Fq2::add(a.c0, b.c0); r.c1 = Fq2::add(a.c1, b.c1); r.c2 = Fq2::add(a.c2, b.c2); return r; }
+  static VZ_HD Fq6 sub(const Fq6& a, const Fq6& b) { Fq6 r; r.c0 = Fq2::sub(a.c0, b.c0); r.c1 = Fq2::sub(a.c1, b.c1); r.c2 = Fq2::sub(a.c2, b.c2); return r; }
+  static VZ_HD Fq6 neg(const Fq6& a) { return sub(zero(), a); }
+  static VZ_HD Fq6 mul(const Fq6& a, const Fq6& b) {      // schoolbook with v³ = ξ
     const Fq2 a0b0 = Fq2::mul(a.c0, b.c0), a1b1 = Fq2::mul(a.c1, b.c1), a2b2 = Fq2::mul(a.c2, b.c2);
     const Fq2 t12 = Fq2::sub(Fq2::sub(Fq2::mul(Fq2::add(a.c1, a.c2), Fq2::add(b.c1, b.c2)), a1b1), a2b2);      // a1 b2 + a2 b1
     const Fq2 t01 = Fq2::sub(Fq2::sub(Fq2::mul(Fq2::add(a.c0, a.c1), Fq2::add(b.c0, b.c1)), a0b0), a1b1);      // a0 b1 + a1 b0
     const Fq2 t02 = Fq2::sub(Fq2::sub(Fq2::mul(Fq2::add(a.c0, a.c2), Fq2::add(b.c0, b.c2)), a0b0), a2b2);      // a0 b2 + a2 b0
     Fq6 r; r.c0 = Fq2::add(a0b0, Fq2::mul_xi(t12)); r.c1 = Fq2::add(t01, Fq2::mul_xi(a2b2)); r.c2 = Fq2::add(t02, a1b1); return r;
   }
-  static Fq6 mul_v(const Fq6& a) { Fq6 r; r.c0 = Fq2::mul_xi(a.c2); r.c1 = a.c0; r.c2 = a.c1; return r; }      // · v
-  static Fq6 inv(const Fq6& a) {
+  static VZ_HD Fq6 mul_v(const Fq6& a) { Fq6 r; r.c0 = Fq2::mul_xi(a.c2); r.c1 = a.c0; r.c2 = a.c1; return r; }      // · v
+  static VZ_HD Fq6 inv(const Fq6& a) {
     const Fq2 A = Fq2::sub(Fq2::sqr(a.c0), Fq2::mul_xi(Fq2::mul(a.c1, a.c2)));
     const Fq2 B = Fq2::sub(Fq2::mul_xi(Fq2::sqr(a.c2)), Fq2::mul(a.c0, a.c1));
     const Fq2 Cc = Fq2::sub(Fq2::sqr(a.c1), Fq2::mul(a.c0, a.c2));
@@ -87,14 +89,14 @@ struct Fq6 {
 
 struct Fq12 {
   Fq6 c0, c1;      // c0 + c1 w
-  static Fq12 one() { Fq12 r; r.c0 = Fq6::one(); r.c1 = Fq6::zero(); return r; }
-  bool is_one() const { return c0.eq(Fq6::one()) && c1.is_zero(); }
-  static Fq12 mul(const Fq12& a, const Fq12& b) {
+  static VZ_HD Fq12 one() { Fq12 r; r.c0 = Fq6::one(); r.c1 = Fq6::zero(); return r; }
+  VZ_HD bool is_one() const { return c0.eq(Fq6::one()) && c1.is_zero(); }
+  static VZ_HD Fq12 mul(const Fq12& a, const Fq12& b) {
     const Fq6 t0 = Fq6::mul(a.c0, b.c0), t1 = Fq6::mul(a.c1, b.c1);
     const Fq6 t2 = Fq6::mul(Fq6::add(a.c0, a.c1), Fq6::add(b.c0, b.c1));
     Fq12 r; r.c0 = Fq6::add(t0, Fq6::mul_v(t1)); r.c1 = Fq6::sub(Fq6::sub(t2, t0), t1); return r;
   }
-  static Fq12 sqr(const Fq12& a) { return mul(a, a); }
+  static VZ_HD Fq12 sqr(const Fq12& a) { return mul(a, a); }
 };
 
 // big exponents as little-endian 32-bit words

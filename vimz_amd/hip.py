@@ -1384,6 +1384,11 @@ class Decider:
         self.ctx._chk(self.ctx.lib.vimz_decider_verify(self.h, int(steps), _ptr(z0a), _ptr(zia), _ptr(wa), C.byref(res)))
         return int(res.value)
 
+    def verify_batch(self, items, chunk=0):
+        """Decider::verify for many (steps, z0, z_i, words) at once, over this decider's key words and context (verify_decider_batch): the list of result bits,
+        each what `verify` gives for that proof alone."""
+        return verify_decider_batch(self.ctx, self.key_words(), items, chunk=chunk)
+
 
 def parse_verifying_key(w):
     w = [int(x) for x in w]
@@ -1447,6 +1452,47 @@ def decider_verify_key(key_words, steps, z0, z_i, words):
     if rc:
         raise L.VimzError(rc, "vimz_decider_verify_key: malformed key or arguments")
     return int(res.value)
+
+
+def verify_decider_batch(ctx, key_words, items, chunk=0, seconds=None, multipliers=None):
+    """vimz_decider_verify_batch: many proofs under one key.  items: a sequence of (steps, z0, z_i, words) as Decider.verify takes them (calldata.decode's
+    "steps", "z0", "z_i", "proof").  ctx: a Context — the per-proof part runs on the GPU — or None: the same batch on the host's threads, no GPU.  Returns the list
+    of result bits, each what decider_verify_key gives for that proof alone.  seconds: a dict that receives the call's split.  multipliers (tests only, testing
+    library): 3 ints a proof in place of the OS's randomness."""
+    lib = L.lib() if ctx is None else ctx.lib
+    vp = C.c_void_p
+    kw = np.ascontiguousarray(key_words, dtype=np.uint64)
+    items = list(items)
+    n = len(items)
+    len_z = len(items[0][1]) if n else 0
+    if any(len(z0) != len_z or len(zi) != len_z or len(w) != 25 for _, z0, zi, w in items):
+        raise L.VimzError(L.ERR_INVALID, "verify_decider_batch: every proof has 25 words and states of one width")
+    if n == 0:
+        len_z = int(kw[4]) if kw.size > 4 else 0
+    steps = np.array([int(s) for s, _, _, _ in items], dtype=np.uint64)
+    z0a = _zlimbs([int(x) for _, z0, _, _ in items for x in z0], n * len_z)
+    zia = _zlimbs([int(x) for _, _, zi, _ in items for x in zi], n * len_z)
+    wa = _zlimbs([int(x) for _, _, _, w in items for x in w], n * 25)
+    res = np.zeros(max(n, 1), dtype=np.uint32)
+    sec = (C.c_double * 6)()
+    head = [None if ctx is None else ctx.h, _ptr(kw), kw.size, len_z, n, _ptr(steps), _ptr(z0a), _ptr(zia), _ptr(wa), int(chunk)]
+    types = [vp, vp, C.c_size_t, C.c_uint32, C.c_size_t, vp, vp, vp, vp, C.c_size_t]
+    if multipliers is None:
+        lib.vimz_decider_verify_batch.argtypes = types + [vp, C.POINTER(C.c_double)]
+        rc = lib.vimz_decider_verify_batch(*head, _ptr(res), sec)
+    else:
+        fn = L.testing_lib().vimz_testing_decider_verify_batch_scalars
+        fn.argtypes = types + [vp, vp, C.POINTER(C.c_double)]
+        ma = np.frombuffer(b"".join(int(x).to_bytes(16, "little") for x in multipliers), dtype="<u8").astype(np.uint64)
+        rc = fn(*head, _ptr(ma), _ptr(res), sec)
+    if rc:
+        if ctx is not None:
+            ctx._chk(rc)
+        lib.vimz_last_error.restype = C.c_char_p
+        raise L.VimzError(rc, (lib.vimz_last_error(None) or b"vimz_decider_verify_batch").decode())
+    if seconds is not None:
+        seconds.update(zip(("parse_and_host", "per_proof_stage", "miller_loops", "chunk_products", "fallback", "total"), (float(x) for x in sec)))
+    return [int(x) for x in res[:n]]
 
 
 class PendingFold:
