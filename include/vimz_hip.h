@@ -842,6 +842,23 @@ size_t vimz_ivc_merged_compressed_size(const vimz_ivc_merged* m);
 int vimz_ivc_merged_compress(vimz_ivc_merged* m, uint8_t* blob, size_t cap, double seconds[2]);
 int vimz_ivc_verify_merged_compressed(vimz_ivc* vk, const uint8_t* blob, size_t len, uint64_t num_steps, const uint64_t* z0, uint32_t* result);
 
+/* MANY compressed proofs under one verifier key in one call (vimz_amd/csrc/spartan_batch.hpp).  blobs[i] / lens[i]: a compressed proof of this family — the
+ * first word tells its kind, one chain or merged, and the two may be mixed; a blob of the other family (or of neither) gets bit 13.  steps[i] and the len_z
+ * elements at z0 + 4·len_z·i are proof i's statement.  results[i] is EXACTLY the word the matching single entry (vimz_ivc_verify_compressed /
+ * vimz_ivc_verify_merged_compressed; vimz_cf_verify_compressed / vimz_cf_verify_merged_compressed) gives for proof i alone.
+ * How: statement, chain hashes, record replay and every scalar check of an argument run per proof on the host's threads, by the single verifiers' own code; the
+ * matrix evaluations M(ry) and the openings' s-vectors run on the GPU for groups of proofs; the openings' final group equations — linear in the proof's points,
+ * the generator U and the key — are summed under non-zero 128-bit multipliers from the OS into ONE equation a curve a chunk: one MSM over the key, one over the
+ * chunk's own points.  chunk: proofs an equation (0 = 32).  An accepted chunk adds no argument bits; a refused chunk, and any proof whose scalar checks fail
+ * inside an argument, is judged member by member by the single verifier (no bisection: one bad proof costs its chunk that many single verifications).
+ * An error code ends the whole call and leaves `results` unspecified: a z0 element not below the modulus (checked for every member before anything is written),
+ * no randomness from the OS, a HIP error.  n = 0 is accepted.  seconds[6] (optional): parse + host checks, half-tables, matrix evaluation, s-vector
+ * accumulation, MSMs, fallback. */
+int vimz_ivc_verify_compressed_batch(vimz_ivc* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0, size_t chunk,
+                                     uint32_t* results, double seconds[6]);
+int vimz_cf_verify_compressed_batch(vimz_cf* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0, size_t chunk,
+                                    uint32_t* results, double seconds[6]);
+
 /* Everything an independent verifier needs, canonical little-endian 4 x u64 per element (the parity tests hand these to the
  * CPU oracle's verifier).  side 0 = primary (BN254 Fr / G1), 1 = secondary (BN254 Fq / Grumpkin).
  *   what = VIMZ_CX_{A,B,C}_{ROWPTR,COL,COEF}, VIMZ_CX_DICT_CANON : the augmented circuit's R1CS

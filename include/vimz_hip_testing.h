@@ -275,6 +275,34 @@ int vimz_test_spartan_instance_pub_verify(vimz_ctx* ctx, int curve, size_t n_c, 
                                           const vimz_bases* ck, const uint64_t digest[4], uint32_t side_tag, const char* label, const uint64_t* inst, int has_E,
                                           const uint64_t* words, size_t n_words);
 
+/* The batched compressed-proof verifier (vimz_amd/csrc/spartan_batch.hpp) piece by piece (tests/test_gpu_spartan_batch.py).  Elements canonical, 4 words each.
+ * _batch_group: members one pass of either kernel serves (a compile-time constant);  _batch_split: the half-table split h.
+ * _mat_eval: out[i] = Σ_m w[i][m] Σ_nonzeros value·eq(rx_i, row)·eq(ry_i, col) over the uploaded shape (triplets as vimz_r1cs_upload takes them, n_c, n_w >= 2) for
+ * n >= 1 members, rx: n·ceil_log2(n_c) elements, ry: n·ceil_log2(n_w), w: n·3 (k_half_tables, k_mat_eval, k_sum_groups, a group at a time).
+ * _svec_accum: n >= 1 openings of `rounds` challenges each (xs, round 0 = the top bit) and a point each; acc_out[j] = Σ_o coefs[o]·s_o[i] over 2^rounds slots,
+ * i = j where shifted[o] = 0, (j + 1) mod 2^rounds where it is not; dots_out[o] = <s_o, eq(point_o, ·)> with the entries i == 0 || i + n_pub[o] >= n_w[o] left out
+ * where n_w[o] != 0 (k_half_tables, k_svec_accum, k_sum_groups).
+ * _instance_batch: n instances over ONE caller's shape, key and digest (as _instance_pub_verify takes one): inst = n × (16 + 4·(1 + n_pub)) words, has_E[i],
+ * words[i] / n_words[i] the argument of instance i.  results[i] = what _instance_pub_verify returns for instance i alone (1 accepted, 0 rejected).  chunk as the
+ * entry points'.  multipliers: NULL (from the OS) or 2 of 2 words an instance (its W opening's, its E opening's; a zero one: VIMZ_ERR_INVALID).  acc_out
+ * (optional): the accumulator of the LAST chunk, next_pow2(max(n_c, n_w)) elements.
+ * _batch_scalars: the two entry points with GIVEN multipliers, 6 of 2 words a proof (the openings of its BN254 arguments in order, W before E, then those of its
+ * Grumpkin arguments; the unused ones must be non-zero too).  Whoever knows the multipliers can make a chunk of wrong proofs pass. */
+int vimz_test_spartan_batch_group(void);
+int vimz_test_spartan_batch_split(void);
+int vimz_test_spartan_mat_eval(vimz_ctx* ctx, int curve, size_t n_c, size_t n_w, const vimz_coo* A, const vimz_coo* B, const vimz_coo* C, size_t n, const uint64_t* rx,
+                               const uint64_t* ry, const uint64_t* w, uint64_t* out);
+int vimz_test_spartan_svec_accum(vimz_ctx* ctx, int field, uint32_t rounds, size_t n, const uint64_t* xs, const uint64_t* points, const uint64_t* coefs, const uint32_t* shifted,
+                                 const uint32_t* n_pub, const uint32_t* n_w, uint64_t* acc_out, uint64_t* dots_out);
+int vimz_test_spartan_instance_batch(vimz_ctx* ctx, int curve, size_t n_c, size_t n_w, uint32_t n_pub, const vimz_coo* A, const vimz_coo* B, const vimz_coo* C,
+                                     const vimz_bases* ck, const uint64_t digest[4], uint32_t side_tag, const char* label, size_t n, const uint64_t* inst, const int* has_E,
+                                     const uint64_t* const* words, const size_t* n_words, size_t chunk, const uint64_t* multipliers, uint32_t* results, double seconds[6],
+                                     uint64_t* acc_out);
+int vimz_testing_ivc_verify_compressed_batch_scalars(vimz_ivc* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0,
+                                                     size_t chunk, const uint64_t* multipliers, uint32_t* results, double seconds[6]);
+int vimz_testing_cf_verify_compressed_batch_scalars(vimz_cf* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0,
+                                                    size_t chunk, const uint64_t* multipliers, uint32_t* results, double seconds[6]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,8 @@ namespace vz {
 int vz_fail(vimz_ctx* c, int code, const char* what, hipError_t e) {
   std::string m = what;
   if (e != hipSuccess) { m += ": "; m += hipGetErrorString(e); }
+  static std::mutex err_mu;          // (host threads of one call may fail side by side: vimz_*_verify_compressed_batch's per-proof pass)
+  std::lock_guard<std::mutex> g(err_mu);
   if (c) c->err = m; else g_err_noctx = m;
   return code;
 }

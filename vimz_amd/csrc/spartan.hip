@@ -301,12 +301,12 @@ int spartan_setup_sides(vimz_ctx* ctx, vimz_prover* p, const cb::Builder& b1, co
 }
 int spartan_setup(vimz_ivc* v, SpartanCache** out) {
   const int rc = spartan_setup_sides(v->ctx, v->pri, v->circ1->build->b, v->sec, v->c2.b, v->ck1, v->ck2, &v->spartan_cache, out);
-  if (!rc) v->spartan_free = spartan_release;
+  if (!rc && v->spartan_free != spartan_release) v->spartan_free = spartan_release;      // (written once: the batch's host threads pass here too)
   return rc;
 }
 int spartan_setup_cf(vimz_cf* v, SpartanCache** out) {
   const int rc = spartan_setup_sides(v->ctx, v->pri, v->circ->build->b, v->sec, v->cf.b, v->ck1, v->ck2, &v->spartan_cache, out);
-  if (!rc) v->spartan_free = spartan_release_cf;
+  if (!rc && v->spartan_free != spartan_release_cf) v->spartan_free = spartan_release_cf;
   return rc;
 }
 
@@ -689,6 +689,18 @@ bool spartan_verify(vimz_ctx* ctx, SpartanCache& cache, SideDev& S, hipStream_t 
   return true;
 }
 
+// How the four verifier entries below judge an argument: SingleVerify is spartan_verify under the context's lock; DeferredVerify (spartan_batch.hpp) replays it on
+// the host and leaves the device and group work to the batch.  Every other line of an entry's body is the same code for both.
+struct SingleVerify {
+  typedef std::lock_guard<std::mutex> Lock;
+  static constexpr bool on_device = true;
+  template <class F, class C, class B>
+  bool arg(vimz_ctx* ctx, SpartanCache& cache, SideDev& S, hipStream_t s, const vimz_bases* ck, const Affine<typename C::Base>& Ugen, const F& digest,
+           const Instance<F, typename C::Base>& I, const B& shape, uint32_t side_tag, Transcript& tr, Reader& in) {
+    return spartan_verify<F, C>(ctx, cache, S, s, ck, Ugen, digest, I, shape, side_tag, tr, in);
+  }
+};
+
 const uint64_t CSNARK_MAGIC = 0x314e5343565aull;   // "ZVCSN1"
 
 struct Loaded {          // the instances a compressed proof is about, as both provers and verifiers hold them
@@ -788,7 +800,10 @@ int vimz_ivc_compress(vimz_ivc* v, uint8_t* blob, size_t cap, double seconds[2])
 // created for the same step circuit and commitment keys (its folding state is neither read nor changed).
 // result: 0 = accepted; bit 0 / 1 the primary / secondary chain hash; bit 2 / 3 / 4 the argument for the primary running /
 // secondary running / last fresh secondary instance; bit 12 the statement (steps, z0) differs; bit 13 malformed proof.
-int vimz_ivc_verify_compressed(vimz_ivc* v, const uint8_t* blob, size_t len, uint64_t num_steps, const uint64_t* z0, uint32_t* result) {
+}  // extern "C"
+namespace {
+template <class V>
+int ivc_verify_compressed_impl(V& vf, vimz_ivc* v, const uint8_t* blob, size_t len, uint64_t num_steps, const uint64_t* z0, uint32_t* result) {
   if (!v || !blob || !z0 || !result) return VIMZ_ERR_INVALID;
   vimz_ctx* ctx = v->ctx;
   SpartanCache* cache = nullptr;
@@ -821,8 +836,8 @@ int vimz_ivc_verify_compressed(vimz_ivc* v, const uint8_t* blob, size_t len, uin
     Fq h2 = instance_hash_native<BnFq>(v->c2.digest, steps, zq, zq, L.U1);
     if (!cross_field<Fe>(h2).eq(L.u2.x1)) res |= 2;
   }
-  std::lock_guard<std::mutex> g(ctx->mu);
-  P_TRY(hipSetDevice(ctx->device));
+  typename V::Lock g(ctx->mu);
+  if (V::on_device) P_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   Transcript tr("vimz-compressed-snark-v1");
   bind_statement(tr, steps, z0p, zn);
@@ -830,9 +845,9 @@ int vimz_ivc_verify_compressed(vimz_ivc* v, const uint8_t* blob, size_t len, uin
   const cb::Builder& b1 = v->circ1->build->b; const cb::BuilderT<Fq>& b2 = v->c2.b;
   bool ok1 = false, ok2 = false, ok3 = false;
   try {
-    ok1 = spartan_verify<Fe, BnG1>(ctx, *cache, cache->side[0], s, v->ck1, cache->ipa_u1, v->c1->digest, inst_primary(L), b1, 1, tr, in);
-    ok2 = ok1 && spartan_verify<Fq, Grumpkin>(ctx, *cache, cache->side[1], s, v->ck2, cache->ipa_u2, v->c2.digest, inst_secondary(L), b2, 2, tr, in);
-    ok3 = ok2 && spartan_verify<Fq, Grumpkin>(ctx, *cache, cache->side[1], s, v->ck2, cache->ipa_u2, v->c2.digest, inst_fresh(L), b2, 3, tr, in);
+    ok1 = vf.template arg<Fe, BnG1>(ctx, *cache, cache->side[0], s, v->ck1, cache->ipa_u1, v->c1->digest, inst_primary(L), b1, 1, tr, in);
+    ok2 = ok1 && vf.template arg<Fq, Grumpkin>(ctx, *cache, cache->side[1], s, v->ck2, cache->ipa_u2, v->c2.digest, inst_secondary(L), b2, 2, tr, in);
+    ok3 = ok2 && vf.template arg<Fq, Grumpkin>(ctx, *cache, cache->side[1], s, v->ck2, cache->ipa_u2, v->c2.digest, inst_fresh(L), b2, 3, tr, in);
   } catch (const std::exception& e) { return vz_fail(ctx, VIMZ_ERR_INVALID, e.what()); }
   if (!ok1) res |= 4;
   if (ok1 && !ok2) res |= 8;
@@ -840,6 +855,12 @@ int vimz_ivc_verify_compressed(vimz_ivc* v, const uint8_t* blob, size_t len, uin
   if (!in.ok || (ok3 && in.pos != in.n)) res |= 8192;
   *result = res;
   return VIMZ_OK;
+}
+}  // namespace
+extern "C" {
+int vimz_ivc_verify_compressed(vimz_ivc* v, const uint8_t* blob, size_t len, uint64_t num_steps, const uint64_t* z0, uint32_t* result) {
+  SingleVerify vf;
+  return ivc_verify_compressed_impl(vf, v, blob, len, num_steps, z0, result);
 }
 
 // ---- CompressedSNARK for a merged proof (merge.hip): one argument for the folded primary instance, one for the folded secondary one.
@@ -891,7 +912,10 @@ int vimz_ivc_merged_compress(vimz_ivc_merged* m, uint8_t* blob, size_t cap, doub
 
 // verify(vk, num_steps, z0) of a compressed merged proof.  result: 0 = accepted; bit 0 / 1 a segment's primary / secondary chain hash;
 // bit 2 / 3 the argument for the folded primary / secondary instance; bit 12 statement (steps, z0, adjacency); bit 13 malformed.
-int vimz_ivc_verify_merged_compressed(vimz_ivc* v, const uint8_t* blob, size_t len, uint64_t num_steps, const uint64_t* z0, uint32_t* result) {
+}  // extern "C"
+namespace {
+template <class V>
+int ivc_verify_merged_compressed_impl(V& vf, vimz_ivc* v, const uint8_t* blob, size_t len, uint64_t num_steps, const uint64_t* z0, uint32_t* result) {
   if (!v || !blob || !z0 || !result) return VIMZ_ERR_INVALID;
   vimz_ctx* ctx = v->ctx;
   SpartanCache* cache = nullptr;
@@ -916,8 +940,8 @@ int vimz_ivc_verify_merged_compressed(vimz_ivc* v, const uint8_t* blob, size_t l
     if (!c.is_reduced()) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_ivc_verify_merged_compressed: z0 element not below the modulus");
     if (!Fe::to_mont(c).eq(R.zs[k])) res |= 4096;
   }
-  std::lock_guard<std::mutex> g(ctx->mu);
-  P_TRY(hipSetDevice(ctx->device));
+  typename V::Lock g(ctx->mu);
+  if (V::on_device) P_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   Transcript tr("vimz-merged-compressed-v1");
   tr.absorb_words("records", words.data() + 2, rw);
@@ -926,14 +950,20 @@ int vimz_ivc_verify_merged_compressed(vimz_ivc* v, const uint8_t* blob, size_t l
   const cb::Builder& b1 = v->circ1->build->b; const cb::BuilderT<Fq>& b2 = v->c2.b;
   bool ok1 = false, ok2 = false;
   try {
-    ok1 = spartan_verify<Fe, BnG1>(ctx, *cache, cache->side[0], s, v->ck1, cache->ipa_u1, v->c1->digest, I1, b1, 1, tr, in);
-    ok2 = ok1 && spartan_verify<Fq, Grumpkin>(ctx, *cache, cache->side[1], s, v->ck2, cache->ipa_u2, v->c2.digest, I2, b2, 2, tr, in);
+    ok1 = vf.template arg<Fe, BnG1>(ctx, *cache, cache->side[0], s, v->ck1, cache->ipa_u1, v->c1->digest, I1, b1, 1, tr, in);
+    ok2 = ok1 && vf.template arg<Fq, Grumpkin>(ctx, *cache, cache->side[1], s, v->ck2, cache->ipa_u2, v->c2.digest, I2, b2, 2, tr, in);
   } catch (const std::exception& e) { return vz_fail(ctx, VIMZ_ERR_INVALID, e.what()); }
   if (!ok1) res |= 4;
   if (ok1 && !ok2) res |= 8;
   if (!in.ok || (ok2 && in.pos != in.n)) res |= 8192;
   *result = res;
   return VIMZ_OK;
+}
+}  // namespace
+extern "C" {
+int vimz_ivc_verify_merged_compressed(vimz_ivc* v, const uint8_t* blob, size_t len, uint64_t num_steps, const uint64_t* z0, uint32_t* result) {
+  SingleVerify vf;
+  return ivc_verify_merged_compressed_impl(vf, v, blob, len, num_steps, z0, result);
 }
 
 
@@ -1015,7 +1045,10 @@ int vimz_cf_compress(vimz_cf* v, uint8_t* blob, size_t cap, double seconds[2]) {
 // verify(vk, num_steps, z0).  `vk`: any vimz_cf created for the same step circuit and commitment keys (its folding state is neither read nor changed).
 // result: 0 = accepted; bit 0 / 1 the hash x0 / x1 carried by u_n; bit 2 / 3 / 4 the argument for U_n / cfU_n / u_n; bit 12 the statement (steps, z0)
 // differs; bit 13 malformed proof (also: a blob of another kind).
-int vimz_cf_verify_compressed(vimz_cf* v, const uint8_t* blob, size_t len, uint64_t num_steps, const uint64_t* z0, uint32_t* result) {
+}  // extern "C"
+namespace {
+template <class V>
+int cf_verify_compressed_impl(V& vf, vimz_cf* v, const uint8_t* blob, size_t len, uint64_t num_steps, const uint64_t* z0, uint32_t* result) {
   if (!v || !blob || !z0 || !result) return VIMZ_ERR_INVALID;
   vimz_ctx* ctx = v->ctx;
   SpartanCache* cache = nullptr;
@@ -1048,8 +1081,8 @@ int vimz_cf_verify_compressed(vimz_cf* v, const uint8_t* blob, size_t len, uint6
   // the two hashes u_n carries, recomputed from the verifier's own digest and the CLAIMED z0
   if (!cf_hash_main(v->c1->digest, steps, z0c, zn.data(), L.U).eq(L.u.x0)) res |= 1;
   if (!cf_hash_cf(v->c1->digest, L.cfU).eq(L.u.x1)) res |= 2;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  P_TRY(hipSetDevice(ctx->device));
+  typename V::Lock g(ctx->mu);
+  if (V::on_device) P_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   Transcript tr("vimz-cf-compressed-v1");
   bind_statement(tr, steps, z0p, zn);
@@ -1058,9 +1091,9 @@ int vimz_cf_verify_compressed(vimz_cf* v, const uint8_t* blob, size_t len, uint6
   const Fq cf_digest = cross_field<Fq>(v->c1->digest);
   bool ok1 = false, ok3 = false, ok2 = false;
   try {
-    ok1 = spartan_verify<Fe, BnG1>(ctx, *cache, cache->side[0], s, v->ck1, cache->ipa_u1, v->c1->digest, cf_inst_running(L), b1, 1, tr, in);
-    ok3 = ok1 && spartan_verify<Fe, BnG1>(ctx, *cache, cache->side[0], s, v->ck1, cache->ipa_u1, v->c1->digest, cf_inst_fresh(L), b1, 3, tr, in);
-    ok2 = ok3 && spartan_verify<Fq, Grumpkin>(ctx, *cache, cache->side[1], s, v->ck2, cache->ipa_u2, cf_digest, cf_inst_cyclefold(L), b2, 2, tr, in);
+    ok1 = vf.template arg<Fe, BnG1>(ctx, *cache, cache->side[0], s, v->ck1, cache->ipa_u1, v->c1->digest, cf_inst_running(L), b1, 1, tr, in);
+    ok3 = ok1 && vf.template arg<Fe, BnG1>(ctx, *cache, cache->side[0], s, v->ck1, cache->ipa_u1, v->c1->digest, cf_inst_fresh(L), b1, 3, tr, in);
+    ok2 = ok3 && vf.template arg<Fq, Grumpkin>(ctx, *cache, cache->side[1], s, v->ck2, cache->ipa_u2, cf_digest, cf_inst_cyclefold(L), b2, 2, tr, in);
   } catch (const std::exception& e) { return vz_fail(ctx, VIMZ_ERR_INVALID, e.what()); }
   if (!ok1) res |= 4;
   if (ok1 && !ok3) res |= 16;
@@ -1068,6 +1101,12 @@ int vimz_cf_verify_compressed(vimz_cf* v, const uint8_t* blob, size_t len, uint6
   if (!in.ok || (ok2 && in.pos != in.n)) res |= 8192;
   *result = res;
   return VIMZ_OK;
+}
+}  // namespace
+extern "C" {
+int vimz_cf_verify_compressed(vimz_cf* v, const uint8_t* blob, size_t len, uint64_t num_steps, const uint64_t* z0, uint32_t* result) {
+  SingleVerify vf;
+  return cf_verify_compressed_impl(vf, v, blob, len, num_steps, z0, result);
 }
 
 size_t vimz_cf_merged_compressed_size(const vimz_cf_merged* m) {
@@ -1113,7 +1152,10 @@ int vimz_cf_merged_compress(vimz_cf_merged* m, uint8_t* blob, size_t cap, double
 
 // verify(vk, num_steps, z0) of a compressed merged Nova + CycleFold proof.  result: 0 = accepted; bit 0 / 1 a segment's main / CycleFold hash; bit 2 / 3
 // the argument for the folded main / CycleFold instance; bit 12 statement (steps, z0, adjacency); bit 13 malformed (also: a blob of another kind).
-int vimz_cf_verify_merged_compressed(vimz_cf* v, const uint8_t* blob, size_t len, uint64_t num_steps, const uint64_t* z0, uint32_t* result) {
+}  // extern "C"
+namespace {
+template <class V>
+int cf_verify_merged_compressed_impl(V& vf, vimz_cf* v, const uint8_t* blob, size_t len, uint64_t num_steps, const uint64_t* z0, uint32_t* result) {
   if (!v || !blob || !z0 || !result) return VIMZ_ERR_INVALID;
   vimz_ctx* ctx = v->ctx;
   SpartanCache* cache = nullptr;
@@ -1139,8 +1181,8 @@ int vimz_cf_verify_merged_compressed(vimz_cf* v, const uint8_t* blob, size_t len
     if (!c.is_reduced()) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_cf_verify_merged_compressed: z0 element not below the modulus");
     if (!Fe::to_mont(c).eq(R.zs[k])) res |= 4096;
   }
-  std::lock_guard<std::mutex> g(ctx->mu);
-  P_TRY(hipSetDevice(ctx->device));
+  typename V::Lock g(ctx->mu);
+  if (V::on_device) P_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   Transcript tr("vimz-cf-merged-compressed-v1");
   tr.absorb_words("records", words.data() + fr.rec_at, fr.rec_words);
@@ -1151,14 +1193,93 @@ int vimz_cf_verify_merged_compressed(vimz_cf* v, const uint8_t* blob, size_t len
   in.pos = fr.args_at;
   bool ok1 = false, ok2 = false;
   try {
-    ok1 = spartan_verify<Fe, BnG1>(ctx, *cache, cache->side[0], s, v->ck1, cache->ipa_u1, v->c1->digest, I1, b1, 1, tr, in);
-    ok2 = ok1 && spartan_verify<Fq, Grumpkin>(ctx, *cache, cache->side[1], s, v->ck2, cache->ipa_u2, cross_field<Fq>(v->c1->digest), I2, b2, 2, tr, in);
+    ok1 = vf.template arg<Fe, BnG1>(ctx, *cache, cache->side[0], s, v->ck1, cache->ipa_u1, v->c1->digest, I1, b1, 1, tr, in);
+    ok2 = ok1 && vf.template arg<Fq, Grumpkin>(ctx, *cache, cache->side[1], s, v->ck2, cache->ipa_u2, cross_field<Fq>(v->c1->digest), I2, b2, 2, tr, in);
   } catch (const std::exception& e) { return vz_fail(ctx, VIMZ_ERR_INVALID, e.what()); }
   if (!ok1) res |= 4;
   if (ok1 && !ok2) res |= 8;
   if (!in.ok || (ok2 && in.pos != in.n)) res |= 8192;
   *result = res;
   return VIMZ_OK;
+}
+}  // namespace
+extern "C" {
+int vimz_cf_verify_merged_compressed(vimz_cf* v, const uint8_t* blob, size_t len, uint64_t num_steps, const uint64_t* z0, uint32_t* result) {
+  SingleVerify vf;
+  return cf_verify_merged_compressed_impl(vf, v, blob, len, num_steps, z0, result);
+}
+
+}  // extern "C"
+
+// ---- many compressed proofs in one call ---------------------------------------------------------------------------------------------------------------------
+#include "spartan_batch.hpp"
+namespace {
+uint64_t first_word(const uint8_t* blob, size_t len) { uint64_t w = 0; if (blob && len >= 8) memcpy(&w, blob, 8); return w; }
+
+int ivc_compressed_batch(const char* who, vimz_ivc* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0, size_t chunk,
+                         const uint64_t* given, uint32_t* results, double seconds[6], BatchProbe* probe) {
+  if (!vk) return VIMZ_ERR_INVALID;
+  vimz_ctx* ctx = vk->ctx;
+  if (n && (!blobs || !lens || !steps || !z0 || !results)) return vz_fail(ctx, VIMZ_ERR_INVALID, "compressed batch: NULL argument");
+  for (size_t i = 0; i < n; i++) if (!blobs[i]) return vz_fail(ctx, VIMZ_ERR_INVALID, "compressed batch: NULL blob");
+  SpartanCache* cache = nullptr;
+  int rc = spartan_setup(vk, &cache);
+  if (rc) return rc;
+  const size_t lz = vk->pri->len_z;
+  // what a caller can get wrong is refused here, on the calling thread, before any result is written (the single entries refuse it proof by proof)
+  for (size_t k = 0; k < 4 * lz * n; k += 4) { Fe c; memcpy(c.v, z0 + k, 32); if (!c.is_reduced()) return vz_fail(ctx, VIMZ_ERR_INVALID, "compressed batch: z0 element not below the modulus"); }
+  auto kind = [&](size_t i) { const uint64_t w = first_word(blobs[i], lens[i]); return w == CSNARK_MAGIC ? 1 : w == CMERGED_MAGIC ? 2 : 0; };
+  auto run = [&](auto& vf, size_t i, uint32_t* res) -> int {
+    switch (kind(i)) {
+      case 1: return ivc_verify_compressed_impl(vf, vk, blobs[i], lens[i], steps[i], z0 + 4 * lz * i, res);
+      case 2: return ivc_verify_merged_compressed_impl(vf, vk, blobs[i], lens[i], steps[i], z0 + 4 * lz * i, res);
+      default: *res = 8192; return VIMZ_OK;      // neither kind of this family
+    }
+  };
+  return compressed_batch(who, ctx, cache, vk->ck1, vk->ck2, n, chunk, given, [&](size_t i, DeferredVerify& vf, uint32_t* res) { return run(vf, i, res); },
+                          [&](size_t i, uint32_t* res) { SingleVerify vf; return run(vf, i, res); }, results, seconds, probe);
+}
+
+int cf_compressed_batch(const char* who, vimz_cf* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0, size_t chunk,
+                        const uint64_t* given, uint32_t* results, double seconds[6], BatchProbe* probe) {
+  if (!vk) return VIMZ_ERR_INVALID;
+  vimz_ctx* ctx = vk->ctx;
+  if (n && (!blobs || !lens || !steps || !z0 || !results)) return vz_fail(ctx, VIMZ_ERR_INVALID, "compressed batch: NULL argument");
+  for (size_t i = 0; i < n; i++) if (!blobs[i]) return vz_fail(ctx, VIMZ_ERR_INVALID, "compressed batch: NULL blob");
+  SpartanCache* cache = nullptr;
+  int rc = spartan_setup_cf(vk, &cache);
+  if (rc) return rc;
+  const size_t lz = vk->pri->len_z;
+  // what a caller can get wrong is refused here, on the calling thread, before any result is written (the single entries refuse it proof by proof)
+  for (size_t k = 0; k < 4 * lz * n; k += 4) { Fe c; memcpy(c.v, z0 + k, 32); if (!c.is_reduced()) return vz_fail(ctx, VIMZ_ERR_INVALID, "compressed batch: z0 element not below the modulus"); }
+  auto kind = [&](size_t i) { const uint64_t w = first_word(blobs[i], lens[i]); return w == cfz::CHAIN_MAGIC ? 1 : w == cfz::MERGED_MAGIC ? 2 : 0; };
+  auto run = [&](auto& vf, size_t i, uint32_t* res) -> int {
+    switch (kind(i)) {
+      case 1: return cf_verify_compressed_impl(vf, vk, blobs[i], lens[i], steps[i], z0 + 4 * lz * i, res);
+      case 2: return cf_verify_merged_compressed_impl(vf, vk, blobs[i], lens[i], steps[i], z0 + 4 * lz * i, res);
+      default: *res = 8192; return VIMZ_OK;
+    }
+  };
+  return compressed_batch(who, ctx, cache, vk->ck1, vk->ck2, n, chunk, given, [&](size_t i, DeferredVerify& vf, uint32_t* res) { return run(vf, i, res); },
+                          [&](size_t i, uint32_t* res) { SingleVerify vf; return run(vf, i, res); }, results, seconds, probe);
+}
+}  // namespace
+
+extern "C" {
+
+// Many compressed proofs under one verifier key in one call.  blobs[i] / lens[i]: what vimz_ivc_compress or vimz_ivc_merged_compress wrote (the first word tells
+// which; the two kinds may be mixed; anything else — a Nova + CycleFold blob among them — gets bit 13); steps[i] and z0 + 4·len_z·i: the statement of proof i.
+// results[i] = the word vimz_ivc_verify_compressed / vimz_ivc_verify_merged_compressed gives for proof i alone.  chunk: proofs an equation (0 = 32); a refused
+// chunk is judged member by member by the single verifier (spartan_batch.hpp).  n = 0 is accepted.  seconds[6] (optional): parse + host checks, half-tables,
+// matrix evaluation, s-vector accumulation, MSMs, fallback.
+int vimz_ivc_verify_compressed_batch(vimz_ivc* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0, size_t chunk,
+                                     uint32_t* results, double seconds[6]) {
+  return ivc_compressed_batch("vimz_ivc_verify_compressed_batch", vk, n, blobs, lens, steps, z0, chunk, nullptr, results, seconds, nullptr);
+}
+// The same for what vimz_cf_compress / vimz_cf_merged_compress wrote; results[i] = vimz_cf_verify_compressed's / vimz_cf_verify_merged_compressed's word.
+int vimz_cf_verify_compressed_batch(vimz_cf* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0, size_t chunk,
+                                    uint32_t* results, double seconds[6]) {
+  return cf_compressed_batch("vimz_cf_verify_compressed_batch", vk, n, blobs, lens, steps, z0, chunk, nullptr, results, seconds, nullptr);
 }
 
 }  // extern "C"
@@ -1431,9 +1552,173 @@ int64_t instance_dispatch(vimz_ctx* ctx, int curve, size_t n_c, size_t n_w, uint
   return out;
 }
 
+// ---- the batch's kernels and its chunk logic on a caller's data (spartan_batch.hpp) ------------------------------------------------------------------------
+template <class F>
+int test_mat_eval(vimz_ctx* ctx, const vimz_r1cs* R, size_t n, const uint64_t* rx, const uint64_t* ry, const uint64_t* w, uint64_t* out) {
+  SideDev S;
+  S.A = R->M[0]; S.B = R->M[1]; S.C = R->M[2]; S.dict = R->dict; S.n_w = (uint32_t)R->ncols; S.n_c = (uint32_t)R->nrows;
+  S.s = ceil_log2(S.n_c); S.t = ceil_log2(S.n_w); S.M = (size_t)1 << S.s; S.N = (size_t)1 << S.t;
+  std::vector<std::vector<F>> px(n), py(n), pw(n);
+  std::vector<const std::vector<F>*> qx(n), qy(n); std::vector<const F*> qw(n);
+  for (size_t i = 0; i < n; i++) {
+    if (!canon_in(rx + 4 * S.s * i, S.s, px[i]) || !canon_in(ry + 4 * S.t * i, S.t, py[i]) || !canon_in(w + 12 * i, 3, pw[i]))
+      return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_mat_eval: element not below the modulus");
+    qx[i] = &px[i]; qy[i] = &py[i]; qw[i] = pw[i].data();
+  }
+  std::lock_guard<std::mutex> g(ctx->mu);
+  P_TRY(hipSetDevice(ctx->device));
+  BatchDev D;
+  P_TRY(D.alloc());
+  std::vector<F> vm;
+  P_TRY(batch_mat_eval<F>(ctx->stream, S, D, qx, qy, qw, vm, nullptr));
+  for (size_t i = 0; i < n; i++) canon_out(out + 4 * i, vm[i]);
+  return VIMZ_OK;
+}
+
+template <class F>
+int test_svec_accum(vimz_ctx* ctx, uint32_t rounds, size_t n, const uint64_t* xs, const uint64_t* pts, const uint64_t* coefs, const uint32_t* shifted, const uint32_t* n_pub,
+                    const uint32_t* n_w, uint64_t* acc_out, uint64_t* dots_out) {
+  std::vector<std::vector<F>> px(n), pp(n); std::vector<F> cf;
+  if (!canon_in(coefs, n, cf)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_svec_accum: element not below the modulus");
+  std::vector<SvecItem<F>> items(n);
+  for (size_t i = 0; i < n; i++) {
+    if (!canon_in(xs + 4 * (size_t)rounds * i, rounds, px[i]) || !canon_in(pts + 4 * (size_t)rounds * i, rounds, pp[i]))
+      return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_svec_accum: element not below the modulus");
+    items[i] = SvecItem<F>{&px[i], &pp[i], cf[i], shifted[i] ? 1u : 0u, n_pub[i], n_w[i]};
+  }
+  const size_t len = (size_t)1 << rounds;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  P_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  BatchDev D;
+  P_TRY(D.alloc());
+  struct Dev { uint32_t *a = nullptr, *b = nullptr; ~Dev() { hipFree(a); hipFree(b); } } d;
+  P_TRY(hipMalloc((void**)&d.a, 32 * len)); P_TRY(hipMalloc((void**)&d.b, 32 * len));
+  P_TRY(hipMemsetAsync(d.a, 0, 32 * len, s));
+  std::vector<F> bfin;
+  P_TRY(batch_svec_accum<F>(s, D, rounds, items, d.a, bfin, nullptr));
+  launch_from_mont<F>(s, d.a, d.b, len);
+  P_TRY(hipGetLastError());
+  P_TRY(hipMemcpyAsync(acc_out, d.b, 32 * len, hipMemcpyDeviceToHost, s));
+  P_TRY(hipStreamSynchronize(s));
+  for (size_t i = 0; i < n; i++) canon_out(dots_out + 4 * i, bfin[i]);
+  return VIMZ_OK;
+}
+
+// one instance's word (1 = accepted) under either policy: what test_instance_verify computes
+template <class F, class C, class V>
+int test_instance_word(V& vf, vimz_ctx* ctx, TestSide& T, SideDev& S, const TestShape<F>& H, const vimz_bases* ck, const Affine<typename C::Base>& Ugen, const F& dg,
+                       uint32_t side_tag, const char* label, const uint64_t* inst, uint32_t n_pub, int has_E, const uint64_t* words, size_t n_words, uint32_t* res) {
+  typedef typename C::Base FS;
+  std::vector<F> sc;
+  std::vector<Affine<FS>> pts;
+  if (!canon_in(inst + 16, 1 + n_pub, sc)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_instance_batch: element not below the modulus");
+  const int bad = points_in(inst, 2, pts);
+  if (bad == 1) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_instance_batch: coordinate not below the modulus");
+  if (bad == 2) { *res = 0; return VIMZ_OK; }
+  Instance<F, FS> I;
+  I.cW = pts[0]; I.cE = pts[1]; I.u = sc[0]; I.n_pub = n_pub; I.has_E = has_E != 0;
+  for (uint32_t k = 0; k < n_pub; k++) I.X[k] = sc[1 + k];
+  typename V::Lock g(ctx->mu);
+  if (V::on_device) P_TRY(hipSetDevice(ctx->device));
+  Transcript tr(label);
+  Reader in{words, n_words};
+  const bool ok = vf.template arg<F, C>(ctx, T.cache, S, ctx->stream, ck, Ugen, dg, I, H, side_tag, tr, in);
+  if (V::on_device) P_TRY(hipStreamSynchronize(ctx->stream));
+  *res = ok && in.ok && in.pos == in.n ? 1u : 0u;
+  return VIMZ_OK;
+}
+
+template <class F, class C>
+int test_instance_batch(vimz_ctx* ctx, int curve, const vimz_r1cs* R, const vimz_bases* ck, const uint64_t digest[4], uint32_t side_tag, const char* label, uint32_t n_pub,
+                        size_t n, const uint64_t* inst, const int* has_E, const uint64_t* const* words, const size_t* n_words, size_t chunk, const uint64_t* multipliers,
+                        uint32_t* results, double seconds[6], uint64_t* acc_out) {
+  typedef typename C::Base FS;
+  std::vector<F> dg;
+  if (!canon_in(digest, 1, dg)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_instance_batch: element not below the modulus");
+  Affine<FS> Ugen;
+  int rc = derive_ipa_u<C>(ctx, curve, &Ugen);
+  if (rc) return rc;
+  TestSide T; TestShape<F> H;
+  {
+    std::lock_guard<std::mutex> g(ctx->mu);
+    P_TRY(hipSetDevice(ctx->device));
+    if ((rc = test_side_build<F>(ctx, R, ck, T, H))) return rc;
+  }
+  const int side = std::is_same<F, Fe>::value ? 0 : 1;
+  if (side == 1) T.cache.side[1] = T.cache.side[0];      // (the Fq side of a batch is side[1]; TestSide frees the scratch through side[0] alone)
+  memcpy(side == 0 ? (void*)&T.cache.ipa_u1 : (void*)&T.cache.ipa_u2, &Ugen, sizeof(Ugen));
+  SideDev& S = T.cache.side[side];
+  const size_t stride = 16 + 4 * (size_t)(1 + n_pub);
+  // a test's multipliers: two an instance (its W opening, its E opening) -> the batch's six a proof
+  std::vector<uint64_t> given;
+  if (multipliers) {
+    given.assign(2 * BATCH_MAX_OPENINGS * n, 1);
+    for (size_t i = 0; i < n; i++) memcpy(&given[2 * BATCH_MAX_OPENINGS * i], multipliers + 4 * i, 32);
+  }
+  BatchProbe probe;
+  if (side == 0) probe.acc[0] = acc_out; else probe.acc[1] = acc_out;
+  auto run = [&](auto& vf, size_t i, uint32_t* res) {
+    return test_instance_word<F, C>(vf, ctx, T, S, H, ck, Ugen, dg[0], side_tag, label, inst + stride * i, n_pub, has_E[i], words[i], n_words[i], res);
+  };
+  return compressed_batch("vimz_test_spartan_instance_batch", ctx, &T.cache, ck, ck, n, chunk, multipliers ? given.data() : nullptr,
+                          [&](size_t i, DeferredVerify& vf, uint32_t* res) { return run(vf, i, res); },
+                          [&](size_t i, uint32_t* res) { SingleVerify vf; return run(vf, i, res); }, results, seconds, acc_out ? &probe : nullptr);
+}
+
 }  // namespace
 
 extern "C" {
+
+int vimz_test_spartan_batch_group(void) { return (int)BATCH_GROUP; }
+int vimz_test_spartan_batch_split(void) { return (int)BATCH_SPLIT_H; }
+
+int vimz_test_spartan_mat_eval(vimz_ctx* ctx, int curve, size_t n_c, size_t n_w, const vimz_coo* A, const vimz_coo* B, const vimz_coo* C, size_t n, const uint64_t* rx,
+                               const uint64_t* ry, const uint64_t* w, uint64_t* out) {
+  if (!ctx || !A || !B || !C || !n || !rx || !ry || !w || !out || (curve != VIMZ_CURVE_BN254_G1 && curve != VIMZ_CURVE_GRUMPKIN) || n_c < 2 || n_w < 2 ||
+      n_c > ((size_t)1 << 21) || n_w > ((size_t)1 << 21) || n > 4096)
+    return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_mat_eval: bad argument");
+  vimz_r1cs* R = nullptr;
+  int rc = vimz_r1cs_upload(ctx, curve == VIMZ_CURVE_BN254_G1 ? VIMZ_FIELD_BN254_FR : VIMZ_FIELD_BN254_FQ, n_c, n_w, A, B, C, VIMZ_FORM_CANONICAL, &R);
+  if (rc) return rc;
+  try { rc = curve == VIMZ_CURVE_BN254_G1 ? test_mat_eval<Fe>(ctx, R, n, rx, ry, w, out) : test_mat_eval<Fq>(ctx, R, n, rx, ry, w, out); }
+  catch (const std::exception& e) { rc = vz_fail(ctx, VIMZ_ERR_INVALID, e.what()); }
+  vimz_r1cs_free(ctx, R);
+  return rc;
+}
+
+int vimz_test_spartan_svec_accum(vimz_ctx* ctx, int field, uint32_t rounds, size_t n, const uint64_t* xs, const uint64_t* points, const uint64_t* coefs, const uint32_t* shifted,
+                                 const uint32_t* n_pub, const uint32_t* n_w, uint64_t* acc_out, uint64_t* dots_out) {
+  if (!ctx || !n || n > 4096 || !xs || !points || !coefs || !shifted || !n_pub || !n_w || !acc_out || !dots_out || rounds < 1 || rounds > 21)
+    return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_svec_accum: bad argument");
+  const int rc = scalar_field_dispatch(field, [&](auto f) { typedef decltype(f) F; return test_svec_accum<F>(ctx, rounds, n, xs, points, coefs, shifted, n_pub, n_w, acc_out, dots_out); });
+  return rc == VIMZ_ERR_INVALID && field != VIMZ_FIELD_BN254_FR && field != VIMZ_FIELD_BN254_FQ ? vz_fail(ctx, rc, "vimz_test_spartan_svec_accum: bad argument") : rc;
+}
+
+int vimz_test_spartan_instance_batch(vimz_ctx* ctx, int curve, size_t n_c, size_t n_w, uint32_t n_pub, const vimz_coo* A, const vimz_coo* B, const vimz_coo* C,
+                                     const vimz_bases* ck, const uint64_t digest[4], uint32_t side_tag, const char* label, size_t n, const uint64_t* inst, const int* has_E,
+                                     const uint64_t* const* words, const size_t* n_words, size_t chunk, const uint64_t* multipliers, uint32_t* results, double seconds[6],
+                                     uint64_t* acc_out) {
+  if (!ctx || !A || !B || !C || !ck || !digest || !label || (n && (!inst || !has_E || !words || !n_words || !results)))
+    return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_instance_batch: bad argument");
+  for (size_t i = 0; i < n; i++) if (!words[i] && n_words[i]) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_instance_batch: bad argument");
+  return (int)instance_dispatch(ctx, curve, n_c, n_w, n_pub, A, B, C, ck, "vimz_test_spartan_instance_batch: bad argument", [&](const vimz_r1cs* R) -> int64_t {
+    return curve == VIMZ_CURVE_BN254_G1
+             ? test_instance_batch<Fe, BnG1>(ctx, curve, R, ck, digest, side_tag, label, n_pub, n, inst, has_E, words, n_words, chunk, multipliers, results, seconds, acc_out)
+             : test_instance_batch<Fq, Grumpkin>(ctx, curve, R, ck, digest, side_tag, label, n_pub, n, inst, has_E, words, n_words, chunk, multipliers, results, seconds, acc_out);
+  });
+}
+
+int vimz_testing_ivc_verify_compressed_batch_scalars(vimz_ivc* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0,
+                                                     size_t chunk, const uint64_t* multipliers, uint32_t* results, double seconds[6]) {
+  if (n && !multipliers) return vz_fail(vk ? vk->ctx : nullptr, VIMZ_ERR_INVALID, "vimz_testing_ivc_verify_compressed_batch_scalars: NULL multipliers");
+  return ivc_compressed_batch("vimz_testing_ivc_verify_compressed_batch_scalars", vk, n, blobs, lens, steps, z0, chunk, multipliers, results, seconds, nullptr);
+}
+int vimz_testing_cf_verify_compressed_batch_scalars(vimz_cf* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0,
+                                                    size_t chunk, const uint64_t* multipliers, uint32_t* results, double seconds[6]) {
+  if (n && !multipliers) return vz_fail(vk ? vk->ctx : nullptr, VIMZ_ERR_INVALID, "vimz_testing_cf_verify_compressed_batch_scalars: NULL multipliers");
+  return cf_compressed_batch("vimz_testing_cf_verify_compressed_batch_scalars", vk, n, blobs, lens, steps, z0, chunk, multipliers, results, seconds, nullptr);
+}
 
 int vimz_test_spartan_eq(vimz_ctx* ctx, int field, const uint64_t* point, size_t k, uint64_t* table_out) {
   if (!ctx || !point || !table_out || k < 1 || k > 21) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_eq: bad argument");

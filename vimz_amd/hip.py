@@ -672,6 +672,11 @@ class IVC:
         self.ctx._chk(lib.vimz_ivc_verify_compressed(self.h, _ptr(b), b.size, int(num_steps), _ptr(z), C.byref(r)))
         return r.value
 
+    def verify_compressed_batch(self, blobs, num_steps, initial_states, chunk=0):
+        """vimz_ivc_verify_compressed_batch: many compressed proofs ("ivc" and "merged" kinds, mixed as they come) under this verifier key in one call.
+        Returns (words, seconds): words[i] is what verify_compressed / MergedProof.verify_compressed gives for proof i alone."""
+        return _compressed_batch(self, "vimz_ivc_verify_compressed_batch", blobs, num_steps, initial_states, chunk)
+
     def export(self, side, what):
         """(n, 4) uint64 canonical elements."""
         return _export(self.ctx.lib.vimz_ivc_export, self.h, side, what).view(np.uint64).reshape(-1, 4)
@@ -767,6 +772,11 @@ class CycleFoldIVC:
         r = C.c_uint32()
         self.ctx._chk(lib.vimz_cf_verify_compressed(self.h, _ptr(b), b.size, int(num_steps), _ptr(_zlimbs(z0, self.circuit.len_z)), C.byref(r)))
         return r.value
+
+    def verify_compressed_batch(self, blobs, num_steps, initial_states, chunk=0):
+        """vimz_cf_verify_compressed_batch: many compressed Nova + CycleFold proofs ("cyclefold" and "cyclefold-merged", mixed) under this verifier key in
+        one call.  Returns (words, seconds): words[i] is what the single verifier gives for proof i alone."""
+        return _compressed_batch(self, "vimz_cf_verify_compressed_batch", blobs, num_steps, initial_states, chunk)
 
     def poke(self, which, index, value):
         """Test hook (vimz_cf_poke, include/vimz_hip_testing.h): exists only when the process runs on libvimz_hip_testing.so
@@ -1728,6 +1738,37 @@ def _zlimbs(z0, len_z):
         for k in range(4):
             z[i, k] = (int(v) >> (64 * k)) & 0xFFFFFFFFFFFFFFFF
     return z
+
+
+def _compressed_batch(vk, entry, blobs, num_steps, initial_states, chunk, multipliers=None):
+    """The shared body of IVC.verify_compressed_batch and CycleFoldIVC.verify_compressed_batch: (flag words, seconds split)."""
+    lib = vk.ctx.lib
+    n = len(blobs)
+    if len(num_steps) != n or len(initial_states) != n:
+        raise L.VimzError(L.ERR_INVALID, f"{entry}: {n} blobs, {len(num_steps)} step counts, {len(initial_states)} initial states")
+    lz = vk.circuit.len_z
+    arrs = [np.ascontiguousarray(np.frombuffer(bytes(b), dtype=np.uint8) if isinstance(b, (bytes, bytearray, memoryview)) else b, dtype=np.uint8).reshape(-1) for b in blobs]
+    keep = [a if a.size else np.zeros(1, dtype=np.uint8) for a in arrs]          # (an empty blob still needs an address)
+    ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in keep])
+    lens = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+    steps = np.array([int(x) for x in num_steps], dtype=np.uint64)
+    z = np.zeros((max(n, 1), lz, 4), dtype=np.uint64)
+    for i, z0 in enumerate(initial_states):
+        z[i] = _zlimbs(z0, lz)
+    res = np.zeros(max(n, 1), dtype=np.uint32)
+    sec = (C.c_double * 6)()
+    vp, sz = C.c_void_p, C.c_size_t
+    fn = getattr(lib, entry)
+    if multipliers is None:
+        fn.argtypes = [vp, sz, vp, vp, vp, vp, sz, vp, C.POINTER(C.c_double)]
+        rc = fn(vk.h, n, ptrs, lens, _ptr(steps), _ptr(z), int(chunk), _ptr(res), sec)
+    else:
+        m = np.ascontiguousarray(multipliers, dtype=np.uint64).reshape(-1)
+        fn.argtypes = [vp, sz, vp, vp, vp, vp, sz, vp, vp, C.POINTER(C.c_double)]
+        rc = fn(vk.h, n, ptrs, lens, _ptr(steps), _ptr(z), int(chunk), _ptr(m), _ptr(res), sec)
+    vk.ctx._chk(rc)
+    names = ("parse_and_host_checks_s", "tables_s", "matrix_evaluation_s", "svec_accumulation_s", "msm_s", "fallback_s")
+    return [int(x) for x in res[:n]], dict(zip(names, list(sec)))
 
 
 class MergedProof:
