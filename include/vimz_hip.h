@@ -735,6 +735,39 @@ int vimz_decider_key_verify_contributions(vimz_ctx* ctx, const void* origin, siz
 #define VIMZ_KEYORIGIN_AT_B2 9
 int vimz_decider_key_verify_origin(vimz_cf* prover, const void* key, size_t len, const uint64_t* tau_g1, size_t n_tau_g1, const uint64_t* tau_g2, const uint64_t* alpha_g1,
                                    const uint64_t* beta_g1, size_t n_pow, const uint64_t beta_g2[16], int form, uint32_t* result, uint64_t first_bad[2], double seconds[5]);
+/* Packed curve points: x and one bit of y, y recovered on the GPU as a square root of x^3 + b when the point is read — half the bytes of a saved key or of a
+ * powers-of-tau string outside snarkjs's container, and a point that unpacks is on its curve by construction.  The encoding is this project's own and canonical, ONE
+ * encoding per point (vimz_amd/csrc/g16_point_pack.hpp).  G1, 4 little-endian words: x as an integer below q; bit 63 of word 3 is INF, bit 62 SIGN = 1 iff the
+ * canonical y is greater than (q - 1)/2; the identity is INF alone (word 3 = 2^63, every other bit 0).  G2, 8 words: x.c0 then x.c1, the flags in the top bits of word
+ * 7, the top two bits of word 3 zero; SIGN = 1 iff y is the larger of (y, -y): y.c1 > (q - 1)/2 when y.c1 != 0, y.c0 > (q - 1)/2 otherwise.  The unpacked side is the
+ * affine layout every other point call takes (G1: x, y in 8 words; G2: x.c0, x.c1, y.c0, y.c1 in 16; the identity as zeros) in `form`; the packed side is always
+ * canonical.  Membership of G2's subgroup of order r is NOT judged here — a point that unpacks is on the twist, no more; it stays where it is judged today
+ * (vimz_decider_key_load for the verifying part, vimz_powers_verify, vimz_decider_key_verify_origin).
+ * _pack / _unpack: n points of `group` (1: G1, 2: G2) through the device in chunks of at most VIMZ_PACK_CHUNK points, one thread per point (peak device memory: one
+ * chunk of input, output and flags — 100 MB for G1, 200 MB for G2).  Return VIMZ_OK whenever the points were judged: a finding is a verdict, not an error.  *result = 0:
+ * done; otherwise the VIMZ_PACK_* bits of the point of lowest index that has a finding, that index in *first_bad, and NOTHING is written to the output.  _COORD: a
+ * coordinate is not below q (when packing, y included);  _FLAGS: INF together with any other bit, or a stray top bit in a G2 word 3;  _OFF_CURVE: x^3 + b is no
+ * square (unpacking), y^2 != x^3 + b (packing).  n = 0 is fine.  The output is written once everything was judged; packed_out may be `points` itself (it is the
+ * smaller); any other overlap of input and output is refused.  seconds (optional) = {host, device with its copies}.  VIMZ_ERR_INVALID: a NULL pointer (seconds
+ * apart; n = 0 included), an unknown group or form, overlapping buffers. */
+#define VIMZ_PACK_CHUNK 1048576
+#define VIMZ_PACK_COORD 0x1u
+#define VIMZ_PACK_FLAGS 0x2u
+#define VIMZ_PACK_OFF_CURVE 0x4u
+int vimz_points_pack(vimz_ctx* ctx, int group, const uint64_t* points, size_t n, int form, uint64_t* packed_out, uint32_t* result, uint64_t* first_bad, double seconds[2]);
+int vimz_points_unpack(vimz_ctx* ctx, int group, const uint64_t* packed, size_t n, int form, uint64_t* points_out, uint32_t* result, uint64_t* first_bad, double seconds[2]);
+/* A saved decider key in half the bytes, and back, on key BYTES (a context is enough, as for vimz_decider_key_contribute).  The packed key: magic "VG16KPK1", words 1..10
+ * of the key verbatim (m, n_pub, n_c, n, len_z, mode, pp_hash), then every point of the key in the key's own order, packed: the KZG [tau]G2, alpha1, beta1, delta1,
+ * beta2, gamma2, delta2, IC, a, b1, l, h, b2 — 55 + 4·((n_pub + 1) + 2m + (m - n_pub - 1) + (n - 1)) + 8m words, 11 + (the key's words - 11)/2; the size follows from the
+ * header alone and is checked against `len` before anything is indexed.  IC‖a‖b1‖l‖h go through the device as one run of G1, b2 as one run of G2; the seven fixed
+ * points are the host's.  unpack(pack(k)) == k byte for byte for every key vimz_decider_key_save writes (zero slots of b2 and of untouched wires included: the
+ * identity packs as INF), and pack(unpack(p)) == p for every packed blob that unpacks.
+ * Return the byte size of the output, or a negative error.  A NULL `out` or a short `cap` returns the size and writes nothing.  *result = 0: done; otherwise the
+ * VIMZ_PACK_* bits of the first point (in the blob's order) that has a finding, first_bad = {the point's offset in 64-bit words in the SOURCE blob, those bits}, and
+ * nothing is written.  `out` may be the input itself (cap says it is large enough); any other overlap is refused.  VIMZ_ERR_INVALID with a message: a NULL pointer,
+ * a blob with the wrong magic or length, overlapping buffers.  vimz_decider_key_save's layout and every call that takes it are unchanged. */
+int64_t vimz_decider_key_pack(vimz_ctx* ctx, const void* key, size_t len, void* out, size_t cap, uint32_t* result, uint64_t first_bad[2]);
+int64_t vimz_decider_key_unpack(vimz_ctx* ctx, const void* packed, size_t len, void* out, size_t cap, uint32_t* result, uint64_t first_bad[2]);
 /* Decider::prove for the IVC proof `ivc` holds (same shapes and keys as the decider's prover; left unchanged; at least one step): final fold, KZG
  * openings, Groth16 proof.  words_out: the 25 calldata words (vimz_amd/calldata.py names them), public_out: the info[2] public inputs; canonical,
  * 4 little-endian limbs each.  VIMZ_ERR_UNSAT when the proof does not satisfy the decider's statement (full decider: including a running CycleFold

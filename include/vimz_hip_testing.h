@@ -303,6 +303,11 @@ int vimz_testing_ivc_verify_compressed_batch_scalars(vimz_ivc* vk, size_t n, con
 int vimz_testing_cf_verify_compressed_batch_scalars(vimz_cf* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0,
                                                     size_t chunk, const uint64_t* multipliers, uint32_t* results, double seconds[6]);
 
+/* The device's square root over Fq2 (vimz_amd/csrc/g16_point_pack.hpp: fq2_sqrt), one thread per value (tests/test_gpu_point_pack.py): values: n elements of Fq2,
+ * c0 then c1, canonical, 4 words each (one not below q: VIMZ_ERR_INVALID); roots_out: the same layout, is_square_out[i] = 1 when roots_out[i] squares to values[i],
+ * 0 when values[i] is no square (the root is then unspecified).  Reaches the branch for c1 = 0, which no curve point one can craft cheaply takes.  1 <= n <= 2^20. */
+int vimz_test_fq2_sqrt(vimz_ctx* ctx, const uint64_t* values, size_t n, uint64_t* roots_out, uint32_t* is_square_out);
+
 #ifdef __cplusplus
 }
 #endif

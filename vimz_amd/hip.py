@@ -1131,7 +1131,9 @@ def contribute_key(ctx, blob, delta=None, nonce=None, seconds=None):
     delta' drawn from the OS and forgotten, the l and h queries times 1/delta' on the GPU, every other byte copied.  Needs a context, no prover: the layout is read
     from the blob's header.  Returns (key bytes, record): uint8 arrays, the record KEYCHAIN_RECORD_BYTES long (this project's own format: include/vimz_hip.h) — keep
     the records of a chain one after another, verify_key_contributions takes them.  delta and nonce (ints, both or neither) select the TEST hook of
-    libvimz_hip_testing.so.  seconds: a list that receives [host, device, total].  VimzError(ERR_INVALID): not a key, a coordinate not below q, a bad delta point."""
+    libvimz_hip_testing.so.  seconds: a list that receives [host, device, total].  VimzError(ERR_INVALID): not a key, a coordinate not below q, a bad delta point.
+    A packed key (pack_key's bytes) is unpacked on the context first, and the key comes back packed: the form it was given."""
+    blob, was_packed = _plain_key(ctx, blob)
     b = np.ascontiguousarray(np.frombuffer(bytes(blob), dtype=np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else blob, dtype=np.uint8)
     out, rec, sec = np.zeros(b.size, dtype=np.uint8), np.zeros(37, dtype=np.uint64), (C.c_double * 3)()
     vp = C.c_void_p
@@ -1151,14 +1153,16 @@ def contribute_key(ctx, blob, delta=None, nonce=None, seconds=None):
         ctx._chk(int(got) if got < 0 else L.ERR_INVALID)
     if seconds is not None:
         seconds[:] = list(sec)
-    return out, rec.view(np.uint8)
+    return (pack_key(ctx, out) if was_packed else out), rec.view(np.uint8)
 
 
 def verify_key_contributions(ctx, origin, final, records, seconds=None):
     """vimz_decider_key_verify_contributions: is `final` the key `origin` after the contributions of `records` (bytes, KEYCHAIN_RECORD_BYTES each, in order; may be
     empty)?  Returns (bits, first_bad): bits 0 = accepted, otherwise a union of KEYCHAIN_BITS; first_bad = (place — KEYCHAIN_PLACES names it —, index).  A verified
     chain means the final key is sound if the origin is and any ONE contributor forgot their delta'.  seconds: a list that receives [host conversion and point checks,
-    per-point flags, combination, equations].  VimzError(ERR_INVALID): a key or a record with the wrong magic or length."""
+    per-point flags, combination, equations].  VimzError(ERR_INVALID): a key or a record with the wrong magic or length.  Either key may be packed (pack_key's bytes):
+    it is unpacked on the context first."""
+    origin, final = _plain_key(ctx, origin)[0], _plain_key(ctx, final)[0]
     as_u8 = lambda x: np.ascontiguousarray(np.frombuffer(bytes(x), dtype=np.uint8) if isinstance(x, (bytes, bytearray, memoryview)) else x, dtype=np.uint8).reshape(-1)      # noqa: E731
     o, f, r = as_u8(origin), as_u8(final), as_u8(records)
     if r.size % KEYCHAIN_RECORD_BYTES:
@@ -1197,9 +1201,10 @@ def verify_key_origin(prover, powers, blob, verify_powers=False, seconds=None):
     verify_key_contributions' matter.  The string is taken as given unless verify_powers is true: the prefix the key's domain reads then goes through hip.verify_powers
     first and a refused string raises VimzError(ERR_INVALID) before any key work.  seconds: a list that receives [circuit synthesis, host conversion + fixed words,
     per-point flags, circuit side, key-side combinations + pairings].  VimzError(ERR_INVALID): not a key, a string shorter than the key's domain needs, a bad point of
-    the string."""
-    b = np.ascontiguousarray(np.frombuffer(bytes(blob), dtype=np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else blob, dtype=np.uint8).reshape(-1)
+    the string.  A packed key (pack_key's bytes) is unpacked on the prover's context first."""
     ctx = prover.ctx
+    blob = _plain_key(ctx, blob)[0]
+    b = np.ascontiguousarray(np.frombuffer(bytes(blob), dtype=np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else blob, dtype=np.uint8).reshape(-1)
     a = {name: np.ascontiguousarray(powers[name], dtype=np.uint64).reshape(-1, 8 * group) for name, group in _LAGRANGE_ARRAYS + (("beta_g2", 2),)}
     n_pow = min(a["tau_g2"].shape[0], a["alpha_g1"].shape[0], a["beta_g1"].shape[0])
     if a["beta_g2"].shape[0] < 1:
@@ -1223,6 +1228,101 @@ def verify_key_origin(prover, powers, blob, verify_powers=False, seconds=None):
 def keyorigin_problems(bits):
     """the names of an origin verdict's bits"""
     return [name for bit, name in KEYORIGIN_BITS.items() if bits & bit]
+
+
+PACK_BITS = {0x1: "a coordinate is not below q", 0x2: "INF together with another bit, or a stray top bit in a G2 word 3", 0x4: "a point is not on its curve"}      # VIMZ_PACK_*
+PACK_BIT_NAMES = ("COORD", "FLAGS", "OFF_CURVE")
+PACKED_KEY_MAGIC, PLAIN_KEY_MAGIC = b"VG16KPK1", b"VG16KEY2"
+
+
+def pack_problems(bits):
+    """the names of a packing verdict's bits"""
+    return [name for bit, name in PACK_BITS.items() if bits & bit]
+
+
+def _as_u8(x):
+    return np.ascontiguousarray(np.frombuffer(bytes(x), dtype=np.uint8) if isinstance(x, (bytes, bytearray, memoryview)) else x, dtype=np.uint8).reshape(-1)
+
+
+def _points_call(ctx, name, group, a, words_out, form, seconds, who):
+    n = a.shape[0]
+    out = np.zeros((n, words_out), dtype=np.uint64)
+    vp = C.c_void_p
+    result, first, sec = C.c_uint32(0), C.c_uint64(0), (C.c_double * 2)()
+    fn = getattr(ctx.lib, name)
+    fn.argtypes = [vp, C.c_int, vp, C.c_size_t, C.c_int, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+    keep = (np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint64))      # (n = 0: the pointers must still be non-NULL)
+    ctx._chk(fn(ctx.h, int(group), _ptr(a) if n else _ptr(keep[0]), n, int(form), _ptr(out) if n else _ptr(keep[1]), C.byref(result), C.byref(first), sec))
+    if seconds is not None:
+        seconds[:] = list(sec)
+    if result.value:
+        raise L.VimzError(L.ERR_INVALID, f"{who}: point {int(first.value)} is refused: " + "; ".join(pack_problems(result.value)) +
+                          f" ({' | '.join(n for k, n in enumerate(PACK_BIT_NAMES) if result.value >> k & 1)} at {int(first.value)})")
+    return out
+
+
+def pack_points(ctx, group, points, form=L.FORM_CANONICAL, seconds=None):
+    """vimz_points_pack: n affine points of G1 (group 1: rows of 8 uint64 words, x then y) or G2 (group 2: rows of 16, x.c0 x.c1 y.c0 y.c1) in `form`, the identity as
+    zeros, to the packed encoding of include/vimz_hip.h — x and one bit of y, half the bytes, always canonical — on the GPU.  Returns rows of 4 (G1) or 8 (G2) words.
+    seconds: a list that receives [host, device with copies].  VimzError(ERR_INVALID) naming the finding (PACK_BITS) and the first point that has one: a coordinate not
+    below q, a point off its curve."""
+    if group not in (1, 2):
+        raise L.VimzError(L.ERR_INVALID, "pack_points: group is 1 (G1) or 2 (G2)")
+    a = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 8 * group)
+    return _points_call(ctx, "vimz_points_pack", group, a, 4 * group, form, seconds, "pack_points")
+
+
+def unpack_points(ctx, group, packed, form=L.FORM_CANONICAL, seconds=None):
+    """vimz_points_unpack: the other way — y is a square root of x³ + b taken on the GPU, so a point that unpacks is on its curve (membership of G2's subgroup is NOT
+    judged: that stays with verify_powers, verify_key_origin and Decider.load_key).  packed: rows of 4 (G1) or 8 (G2) words; returns rows of 8 or 16 in `form`.
+    VimzError(ERR_INVALID) naming the finding and the first point that has one: a coordinate not below q, bad flag bits, an x with no y."""
+    if group not in (1, 2):
+        raise L.VimzError(L.ERR_INVALID, "unpack_points: group is 1 (G1) or 2 (G2)")
+    a = np.ascontiguousarray(packed, dtype=np.uint64).reshape(-1, 4 * group)
+    return _points_call(ctx, "vimz_points_unpack", group, a, 8 * group, form, seconds, "unpack_points")
+
+
+def key_is_packed(blob):
+    """does the blob start with a packed key's magic?  (Nothing else is looked at.)"""
+    return bytes(_as_u8(blob)[:8]) == PACKED_KEY_MAGIC
+
+
+def _key_call(ctx, name, blob, who):
+    b = _as_u8(blob)
+    vp = C.c_void_p
+    fn = getattr(ctx.lib, name)
+    fn.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_uint32), vp]
+    fn.restype = C.c_int64
+    result, first = C.c_uint32(0), np.zeros(2, dtype=np.uint64)
+    n = fn(ctx.h, _ptr(b), b.size, None, 0, C.byref(result), _ptr(first))
+    if n < 0:
+        ctx._chk(int(n))
+    out = np.zeros(n, dtype=np.uint8)
+    got = fn(ctx.h, _ptr(b), b.size, _ptr(out), n, C.byref(result), _ptr(first))
+    if got != n:
+        ctx._chk(int(got) if got < 0 else L.ERR_INVALID)
+    if result.value:
+        raise L.VimzError(L.ERR_INVALID, f"{who}: the point at word {int(first[0])} of the blob is refused: " + "; ".join(pack_problems(result.value)) +
+                          f" ({' | '.join(n for k, n in enumerate(PACK_BIT_NAMES) if result.value >> k & 1)} at word {int(first[0])})")
+    return out
+
+
+def pack_key(ctx, blob):
+    """vimz_decider_key_pack: a saved decider key (Decider.save_key's bytes) in half the bytes — the header verbatim under the magic "VG16KPK1", every point packed,
+    the queries on the GPU.  Needs a context, no prover.  Returns a uint8 array.  VimzError(ERR_INVALID): not a key, or a point of it with a coordinate not below q or
+    off its curve (the message names the point's word offset in the blob)."""
+    return _key_call(ctx, "vimz_decider_key_pack", blob, "pack_key")
+
+
+def unpack_key(ctx, blob):
+    """vimz_decider_key_unpack: Decider.save_key's bytes from a packed key, byte for byte — every point on its curve by construction.  VimzError(ERR_INVALID): not a
+    packed key, or a point that does not unpack."""
+    return _key_call(ctx, "vimz_decider_key_unpack", blob, "unpack_key")
+
+
+def _plain_key(ctx, blob):
+    """(the key in Decider.save_key's layout, whether it came packed)"""
+    return (unpack_key(ctx, blob), True) if key_is_packed(blob) else (blob, False)
 
 
 def set_head_rows(rows):
@@ -1322,8 +1422,9 @@ class Decider:
             self.ctx.lib.vimz_decider_free(self.h)
             self.h = None
 
-    def save_key(self):
-        """vimz_decider_key_save: the key pair as bytes (uint8 array; 0.5 GB at contrast HD)."""
+    def save_key(self, packed=False):
+        """vimz_decider_key_save: the key pair as bytes (uint8 array; 0.5 GB at contrast HD).  packed=True: through vimz_decider_key_pack — every point as x and one
+        bit of y, about half the bytes (hip.pack_key); load_key and the key calls take either form."""
         lib = self.ctx.lib
         lib.vimz_decider_key_save.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         lib.vimz_decider_key_save.restype = C.c_int64
@@ -1334,11 +1435,13 @@ class Decider:
         got = lib.vimz_decider_key_save(self.h, _ptr(buf), n)
         if got != n:
             self.ctx._chk(int(got) if got < 0 else L.ERR_INVALID)
-        return buf
+        return pack_key(self.ctx, buf) if packed else buf
 
     @classmethod
     def load_key(cls, prover, blob):
-        """vimz_decider_key_load: a decider over `prover` (a CycleFoldIVC) from a saved — or externally made — key pair; no trapdoor is involved."""
+        """vimz_decider_key_load: a decider over `prover` (a CycleFoldIVC) from a saved — or externally made — key pair; no trapdoor is involved.  A packed key
+        (save_key(packed=True), hip.pack_key) is unpacked on the prover's context first.  .light is the mode the key's header names."""
+        blob = _plain_key(prover.ctx, blob)[0]
         d = cls.__new__(cls)
         d.prover, d.ctx = prover, prover.ctx
         lib = d.ctx.lib
@@ -1355,6 +1458,7 @@ class Decider:
         h = vp()
         d.ctx._chk(lib.vimz_decider_key_load(prover.h, _ptr(b), b.size, C.byref(h)))
         d.h = h
+        d.light = bool(int.from_bytes(b[48:56].tobytes(), "little"))      # header word 6: 0 full, 1 light
         d._kzg_vk = None
         d.setup_seconds = {"circuit_synthesis": 0.0, "qap_at_trapdoor_host": 0.0, "key_points_gpu": 0.0, "total": 0.0}
         return d

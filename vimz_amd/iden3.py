@@ -147,6 +147,52 @@ def new_powers(power):
             "beta_g1": np.tile(g1, (n2, 1)), "beta_g2": np.tile(g2, (1, 1))}
 
 
+_PACKED_POWERS_MAGIC = b"VPOTPK01"
+
+
+def pack_powers(ctx, powers):
+    """read_ptau's dictionary -> bytes of this project's own container for a string at rest, half the size of the `.ptau`'s point sections: magic "VPOTPK01", power and
+    ceremony_power (u32 each), then the five arrays in _PTAU_SECTIONS order, every point packed on the GPU (hip.pack_points: x and one bit of y, canonical).  `.ptau`
+    itself stays snarkjs's layout.  VimzError(ERR_INVALID): a point with a coordinate not below q or off its curve; ValueError: an array whose shape does not match
+    the power."""
+    from . import hip
+    power = int(powers["power"])
+    if not 1 <= power <= 26:
+        raise ValueError("pack_powers: power outside 1..26")
+    n2 = 1 << power
+    parts = [_PACKED_POWERS_MAGIC + struct.pack("<II", power, int(powers.get("ceremony_power", power)))]
+    for _t, name, size in _PTAU_SECTIONS:
+        points = {"tau_g1": 2 * n2 - 1, "beta_g2": 1}.get(name, n2)
+        a = np.ascontiguousarray(powers[name], dtype=np.uint64)
+        if a.size != points * size // 8:
+            raise ValueError(f"pack_powers: {name} holds {a.size * 8} bytes, the power asks for {points * size}")
+        parts.append(hip.pack_points(ctx, size // 64, a, form=hip.L.FORM_MONTGOMERY).astype("<u8").tobytes())
+    return b"".join(parts)
+
+
+def unpack_powers(ctx, data):
+    """pack_powers' bytes -> read_ptau's dictionary (rows in the file's Montgomery form; write_ptau takes it): every point unpacked on the GPU, so each is on its
+    curve — subgroup membership and the string's equations remain hip.verify_powers' matter.  ValueError: not such a container or the wrong length for its power;
+    VimzError(ERR_INVALID): a point that does not unpack."""
+    from . import hip
+    data = bytes(data)
+    if len(data) < 16 or data[:8] != _PACKED_POWERS_MAGIC:
+        raise ValueError("unpack_powers: not a packed powers-of-tau string")
+    power, ceremony_power = struct.unpack_from("<II", data, 8)
+    if not 1 <= power <= 26:
+        raise ValueError("unpack_powers: power outside 1..26")
+    n2 = 1 << power
+    counts = [({"tau_g1": 2 * n2 - 1, "beta_g2": 1}.get(name, n2), name, size) for _t, name, size in _PTAU_SECTIONS]
+    if len(data) != 16 + sum(points * size // 2 for points, _name, size in counts):
+        raise ValueError(f"unpack_powers: {len(data)} bytes, the power asks for {16 + sum(points * size // 2 for points, _name, size in counts)}")
+    out, pos = {"power": power, "ceremony_power": ceremony_power}, 16
+    for points, name, size in counts:
+        rows = np.frombuffer(data, dtype="<u8", count=points * size // 16, offset=pos).reshape(points, size // 16)
+        out[name] = hip.unpack_points(ctx, size // 64, rows, form=hip.L.FORM_MONTGOMERY)
+        pos += points * size // 2
+    return out
+
+
 def to_nova_columns(r1cs):
     """The matrices with circom wire j moved to nova-snark's column: j = 0 -> the u slot, 1 <= j <= n_pub -> X, the rest -> W.
     -> (n_witness, n_public, A, B, C)."""
@@ -170,11 +216,12 @@ def split_witness(r1cs, wtns_values):
 
 
 def _decider_key(argv):
-    """decider-key FILE.ptau TRANSFORMATION RESOLUTION OUT.key [--light] [--verify]: the decider's Groth16 key pair for that step circuit, derived from the string on GPU 0
-    (hip.Decider(powers=): tau, alpha, beta are the string's, delta is drawn here and forgotten), as vimz_decider_key_save's bytes.  --verify: the prefixes of the
-    string the SRS and the set-up read are judged first (hip.verify_powers); a refused string ends the command with VimzError."""
-    light, verify = "--light" in argv, "--verify" in argv
-    args = [a for a in argv if a not in ("--light", "--verify")]
+    """decider-key FILE.ptau TRANSFORMATION RESOLUTION OUT.key [--light] [--verify] [--packed]: the decider's Groth16 key pair for that step circuit, derived from the
+    string on GPU 0 (hip.Decider(powers=): tau, alpha, beta are the string's, delta is drawn here and forgotten), as vimz_decider_key_save's bytes — with --packed as
+    vimz_decider_key_pack's, about half of them.  --verify: the prefixes of the string the SRS and the set-up read are judged first (hip.verify_powers); a refused
+    string ends the command with VimzError."""
+    light, verify, packed = "--light" in argv, "--verify" in argv, "--packed" in argv
+    args = [a for a in argv if a not in ("--light", "--verify", "--packed")]
     if len(args) != 5 or any(a.startswith("--") for a in args):
         print(USAGE, file=sys.stderr)
         return 2
@@ -188,7 +235,7 @@ def _decider_key(argv):
         try:
             dec = params.decider(cf, light=light)
             try:
-                blob, info, sec = dec.save_key(), dec.info(), dec.setup_seconds
+                blob, info, sec = dec.save_key(packed=packed), dec.info(), dec.setup_seconds
             finally:
                 dec.close()
         finally:
@@ -197,7 +244,7 @@ def _decider_key(argv):
         ctx.close()
     with open(args[4], "wb") as fp:
         blob.tofile(fp)
-    print(f"decider-key: {'light' if light else 'full'} decider of {args[2]} {args[3]}, domain {info['domain']}, {blob.size} bytes -> {args[4]} (set-up {sec['total']:.1f} s)")
+    print(f"decider-key: {'light' if light else 'full'} decider of {args[2]} {args[3]}, domain {info['domain']}, {blob.size} bytes{' (packed)' if packed else ''} -> {args[4]} (set-up {sec['total']:.1f} s)")
     return 0
 
 
@@ -229,7 +276,7 @@ def _verify(argv):
 
 def _contribute(argv):
     """contribute IN.key OUT.key RECORDS: one further delta contribution to a saved decider key on GPU 0 (hip.contribute_key: delta' is drawn here and forgotten);
-    the contributed key goes to OUT.key and the 296-byte record is APPENDED to RECORDS (this project's own format, not snarkjs's .zkey)."""
+    the contributed key goes to OUT.key — packed if IN.key is — and the 296-byte record is APPENDED to RECORDS (this project's own format, not snarkjs's .zkey)."""
     if len(argv) != 4:
         print(USAGE, file=sys.stderr)
         return 2
@@ -252,7 +299,7 @@ def _contribute(argv):
 
 def _verify_contributions(argv):
     """verify-contributions ORIGIN.key FINAL.key RECORDS: judges the chain on GPU 0 (hip.verify_key_contributions), prints the verdict and the times; exit status 0
-    accepted, 1 refused.  Accepted means: FINAL.key is sound if ORIGIN.key is and any one contributor forgot their delta'."""
+    accepted, 1 refused.  Accepted means: FINAL.key is sound if ORIGIN.key is and any one contributor forgot their delta'.  Either key may be packed."""
     if len(argv) != 4:
         print(USAGE, file=sys.stderr)
         return 2
@@ -275,7 +322,7 @@ def _verify_contributions(argv):
 
 
 def _verify_key(argv):
-    """verify-key FILE.ptau TRANSFORMATION RESOLUTION KEY [--verify]: judges on GPU 0 that KEY (vimz_decider_key_save's bytes, from anyone) is the key a set-up from the
+    """verify-key FILE.ptau TRANSFORMATION RESOLUTION KEY [--verify]: judges on GPU 0 that KEY (vimz_decider_key_save's bytes or a packed key, from anyone) is the key a set-up from the
     string derives for that step circuit's decider — light or full as the key says —, for the delta its delta points commit to (hip.verify_key_origin); prints the
     verdict's bit names and the times; exit status 0 accepted, 1 refused.  --verify: the string's prefixes are judged first (hip.verify_powers)."""
     verify = "--verify" in argv
@@ -377,15 +424,59 @@ def _verify_powers_contributions(argv):
     return 1
 
 
+def _pack_key(argv):
+    """pack-key IN OUT / unpack-key IN OUT: a saved decider key to its packed form (hip.pack_key: every point as x and one bit of y, about half the bytes) and back
+    (hip.unpack_key: vimz_decider_key_save's bytes, byte for byte) on GPU 0.  A point that is refused ends the command with VimzError."""
+    if len(argv) != 3:
+        print(USAGE, file=sys.stderr)
+        return 2
+    from . import hip
+    blob = np.fromfile(argv[1], dtype=np.uint8)
+    ctx = hip.Context(0)
+    try:
+        out = (hip.pack_key if argv[0] == "pack-key" else hip.unpack_key)(ctx, blob)
+    finally:
+        ctx.close()
+    with open(argv[2], "wb") as fp:
+        out.tofile(fp)
+    print(f"{argv[0]}: {argv[1]} ({blob.size} bytes) -> {argv[2]} ({out.size} bytes)")
+    return 0
+
+
+def _pack_powers(argv):
+    """pack-powers FILE.ptau OUT: the string in this project's packed container (pack_powers) on GPU 0.  unpack-powers IN FILE.ptau: back to a `.ptau` (unpack_powers,
+    write_ptau).  A point that is refused ends the command with VimzError."""
+    if len(argv) != 3:
+        print(USAGE, file=sys.stderr)
+        return 2
+    from . import hip
+    with open(argv[1], "rb") as fp:
+        data = fp.read()
+    ctx = hip.Context(0)
+    try:
+        out = pack_powers(ctx, read_ptau(data)) if argv[0] == "pack-powers" else write_ptau(unpack_powers(ctx, data))
+    finally:
+        ctx.close()
+    with open(argv[2], "wb") as fp:
+        fp.write(out)
+    print(f"{argv[0]}: {argv[1]} ({len(data)} bytes) -> {argv[2]} ({len(out)} bytes)")
+    return 0
+
+
 USAGE = ("usage: python -m vimz_amd.iden3 lagrange FILE.ptau LOGN OUT.npz\n"
          "       python -m vimz_amd.iden3 new-powers POWER OUT.ptau\n"
          "       python -m vimz_amd.iden3 contribute-powers IN.ptau OUT.ptau RECORDS\n"
          "       python -m vimz_amd.iden3 verify-powers-contributions ORIGIN.ptau FINAL.ptau RECORDS\n"
-         "       python -m vimz_amd.iden3 decider-key FILE.ptau TRANSFORMATION RESOLUTION OUT.key [--light] [--verify]\n"
+         "       python -m vimz_amd.iden3 decider-key FILE.ptau TRANSFORMATION RESOLUTION OUT.key [--light] [--verify] [--packed]\n"
          "       python -m vimz_amd.iden3 verify FILE.ptau [POINTS]\n"
          "       python -m vimz_amd.iden3 contribute IN.key OUT.key RECORDS\n"
          "       python -m vimz_amd.iden3 verify-contributions ORIGIN.key FINAL.key RECORDS\n"
-         "       python -m vimz_amd.iden3 verify-key FILE.ptau TRANSFORMATION RESOLUTION KEY [--verify]")
+         "       python -m vimz_amd.iden3 verify-key FILE.ptau TRANSFORMATION RESOLUTION KEY [--verify]\n"
+         "       python -m vimz_amd.iden3 pack-key IN.key OUT\n"
+         "       python -m vimz_amd.iden3 unpack-key IN OUT.key\n"
+         "       python -m vimz_amd.iden3 pack-powers FILE.ptau OUT\n"
+         "       python -m vimz_amd.iden3 unpack-powers IN FILE.ptau\n"
+         "(the key commands take a key in either form, vimz_decider_key_save's or packed)")
 
 
 def _main(argv):
@@ -393,7 +484,12 @@ def _main(argv):
     as an .npz of tau_g1, alpha_g1, beta_g1 (n, 8) and tau_g2 (n, 16) in the file's Montgomery form, with logn.
     python -m vimz_amd.iden3 decider-key ...: _decider_key.  python -m vimz_amd.iden3 verify ...: _verify.
     python -m vimz_amd.iden3 contribute ... / verify-contributions ... / verify-key ...: _contribute, _verify_contributions, _verify_key.
-    python -m vimz_amd.iden3 new-powers ... / contribute-powers ... / verify-powers-contributions ...: _new_powers, _contribute_powers, _verify_powers_contributions."""
+    python -m vimz_amd.iden3 new-powers ... / contribute-powers ... / verify-powers-contributions ...: _new_powers, _contribute_powers, _verify_powers_contributions.
+    python -m vimz_amd.iden3 pack-key ... / unpack-key ...: _pack_key.  python -m vimz_amd.iden3 pack-powers ... / unpack-powers ...: _pack_powers."""
+    if argv and argv[0] in ("pack-key", "unpack-key"):
+        return _pack_key(argv)
+    if argv and argv[0] in ("pack-powers", "unpack-powers"):
+        return _pack_powers(argv)
     if argv and argv[0] == "new-powers":
         return _new_powers(argv)
     if argv and argv[0] == "contribute-powers":
