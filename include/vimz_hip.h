@@ -786,16 +786,32 @@ int vimz_decider_verify_key(const uint64_t* key_words, size_t n_key_words, uint6
  * else, a public element not below r gives 8 without the KZG bits, steps < 2 gives bit 1 and the checks go on).
  * Proofs that pass the per-proof stage are cut into chunks of `chunk` (0: 256).  Under three 128-bit multipliers a proof from the OS, wiped after use on host
  * and device, a chunk is accepted iff ONE product of Miller values is one after ONE final exponentiation (vimz_amd/csrc/decider_batch.hpp states it; wrong with
- * probability about 2^-128); a refused chunk is judged member by member by the single verifier on the host's threads — no bisection: one bad proof costs its chunk
- * `chunk` single verifications.  Every proof's B passes "on the twist" and r·B = O by itself before it enters a product.
+ * probability about 2^-128); a refused chunk is bisected: the same equation is asked of halves from the rows and Miller values that are already there, a member is
+ * accepted only inside a subset whose equation was evaluated and held, and a refused subset of at most `leaf` members is judged member by member by the single
+ * verifier on the host's threads (at most 2·(chunk − 1) subset equations a refused chunk; vimz_decider_verify_batch_ex has the switches and the counts).
+ * Every proof's B passes "on the twist" and r·B = O by itself before it enters a product.
  * ctx != NULL: what grows with the batch runs on the GPU — the curve and subgroup flags of every point (k_powers_flags), twelve G1 scalar multiplications a proof
  * and the per-chunk sums (k_g1_lincomb, k_col_runs), one Miller loop a proof (k_miller: homogeneous projective steps, sparse line products) —, the five
  * fixed-G2 Miller loops and the final exponentiation of each chunk on the host.  ctx == NULL: every device stage is its host loop over the same per-thread
  * functions on up to 16 threads — the path of a machine without a GPU.  n == 0 is VIMZ_OK.  A NULL pointer, an unparsable key or a len_z that is not the key's:
  * VIMZ_ERR_INVALID with a message (vimz_last_error(ctx); of the calling thread when ctx is NULL).
- * seconds (optional) = {parse + per-proof host work, per-proof device stage, Miller loops, host sums + fixed-G2 loops + final exponentiations, fallback, total} */
+ * seconds (optional) = {parse + per-proof host work, per-proof device stage, Miller loops, host sums + fixed-G2 loops + final exponentiations, fallback (the
+ * subset equations of refused chunks and the single verifications), total} */
 int vimz_decider_verify_batch(vimz_ctx* ctx, const uint64_t* key_words, size_t n_key_words, uint32_t len_z, size_t n, const uint64_t* steps, const uint64_t* z0,
                               const uint64_t* zi, const uint64_t* words, size_t chunk, uint32_t* results, double seconds[6]);
+/* The batch verifiers' _ex entries: the entry of the same name with
+ *   flags  VIMZ_BATCH_NO_BISECT: a refused chunk goes member by member to the single verifier, whole (any other bit: VIMZ_ERR_INVALID);
+ *   leaf   a refused subset of at most `leaf` members goes to the single verifier; 0: the default (decider 128 on the device and 64 with
+ *          ctx == NULL, compressed 1: profiles/batch_bisect.txt has the measurements behind them);
+ *   stats  (optional) = {chunks refused, subset equations evaluated after a refusal (one a side asked: the compressed verifiers have two curves, and a subset is
+ *          asked only on the sides its parent was refused on), single verifications run, members of refused chunks accepted by a subset equation}.
+ * `results` are the same words whatever flags and leaf are: a member is accepted by an evaluated equation over a subset it lies in, or judged by the single
+ * verifier (vimz_amd/csrc/batch_bisect.hpp).  The entries without _ex are these with flags = 0, leaf = 0, stats = NULL.  The compressed verifiers' twins are
+ * vimz_ivc_verify_batch_compressed_ex and vimz_cf_verify_batch_compressed_ex ("verify_batch" as the decider's entry has it). */
+#define VIMZ_BATCH_NO_BISECT 1u
+int vimz_decider_verify_batch_ex(vimz_ctx* ctx, const uint64_t* key_words, size_t n_key_words, uint32_t len_z, size_t n, const uint64_t* steps, const uint64_t* z0,
+                                 const uint64_t* zi, const uint64_t* words, size_t chunk, uint32_t* results, double seconds[6], uint32_t flags, size_t leaf,
+                                 uint64_t stats[4]);
 
 /* ---- ONE proof object out of several row segments: the "host-side sequential final fold" of BASELINE.json's north_star for IVC proofs.
  *      fold_input returns ONE RecursiveSNARK (vimz/src/nova_snark_backend/folding.rs:27-43); row segments of an image folded
@@ -883,14 +899,21 @@ int vimz_ivc_verify_merged_compressed(vimz_ivc* vk, const uint8_t* blob, size_t 
  * matrix evaluations M(ry) and the openings' s-vectors run on the GPU for groups of proofs; the openings' final group equations — linear in the proof's points,
  * the generator U and the key — are summed under non-zero 128-bit multipliers from the OS into ONE equation a curve a chunk: one MSM over the key, one over the
  * chunk's own points.  chunk: proofs an equation (0 = 32).  An accepted chunk adds no argument bits; a refused chunk, and any proof whose scalar checks fail
- * inside an argument, is judged member by member by the single verifier (no bisection: one bad proof costs its chunk that many single verifications).
+ * inside an argument, goes to the single verifier — the refused chunk through a bisection: the two equations are asked again of halves of the chunk, every
+ * member under the multipliers it had and from the arguments already replayed (nothing is recomputed per proof), a half only on the curves its parent was refused
+ * on; a member is accepted only inside a subset whose equations were evaluated and held, and a refused subset of at most `leaf` members is judged member by member
+ * by the single verifier.  At most 2·(chunk − 1) subsets are asked of a refused chunk.  The _ex entries (see vimz_decider_verify_batch_ex) have the switches.
  * An error code ends the whole call and leaves `results` unspecified: a z0 element not below the modulus (checked for every member before anything is written),
  * no randomness from the OS, a HIP error.  n = 0 is accepted.  seconds[6] (optional): parse + host checks, half-tables, matrix evaluation, s-vector
- * accumulation, MSMs, fallback. */
+ * accumulation, MSMs, fallback (the subset equations of refused chunks and the single verifications). */
 int vimz_ivc_verify_compressed_batch(vimz_ivc* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0, size_t chunk,
                                      uint32_t* results, double seconds[6]);
 int vimz_cf_verify_compressed_batch(vimz_cf* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0, size_t chunk,
                                     uint32_t* results, double seconds[6]);
+int vimz_ivc_verify_batch_compressed_ex(vimz_ivc* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0, size_t chunk,
+                                        uint32_t* results, double seconds[6], uint32_t flags, size_t leaf, uint64_t stats[4]);
+int vimz_cf_verify_batch_compressed_ex(vimz_cf* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0, size_t chunk,
+                                       uint32_t* results, double seconds[6], uint32_t flags, size_t leaf, uint64_t stats[4]);
 
 /* Everything an independent verifier needs, canonical little-endian 4 x u64 per element (the parity tests hand these to the
  * CPU oracle's verifier).  side 0 = primary (BN254 Fr / G1), 1 = secondary (BN254 Fq / Grumpkin).

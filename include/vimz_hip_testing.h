@@ -235,6 +235,10 @@ int vimz_test_g1_lincomb(vimz_ctx* ctx, const uint64_t* a_xy, const uint64_t* k,
  * Whoever knows the multipliers can make a chunk of wrong proofs pass: two proofs with their C points swapped pass under multipliers that are all one. */
 int vimz_testing_decider_verify_batch_scalars(vimz_ctx* ctx, const uint64_t* key_words, size_t n_key_words, uint32_t len_z, size_t n, const uint64_t* steps, const uint64_t* z0,
                                               const uint64_t* zi, const uint64_t* words, size_t chunk, const uint64_t* multipliers, uint32_t* results, double seconds[6]);
+/* the same with vimz_decider_verify_batch_ex's flags, leaf and stats */
+int vimz_testing_decider_verify_batch_scalars_ex(vimz_ctx* ctx, const uint64_t* key_words, size_t n_key_words, uint32_t len_z, size_t n, const uint64_t* steps,
+                                                 const uint64_t* z0, const uint64_t* zi, const uint64_t* words, size_t chunk, const uint64_t* multipliers,
+                                                 uint32_t* results, double seconds[6], uint32_t flags, size_t leaf, uint64_t stats[4]);
 
 /* The compressed proof's kernels (vimz_amd/csrc/spartan.hip) on a caller's vectors, through the functions spartan_prove and ipa_prove run for every round
  * (tests/test_gpu_spartan_kernels.py).  field = VIMZ_FIELD_BN254_FR or _FQ, curve = VIMZ_CURVE_BN254_G1 or _GRUMPKIN (anything else: VIMZ_ERR_INVALID); elements are
@@ -287,7 +291,9 @@ int vimz_test_spartan_instance_pub_verify(vimz_ctx* ctx, int curve, size_t n_c, 
  * entry points'.  multipliers: NULL (from the OS) or 2 of 2 words an instance (its W opening's, its E opening's; a zero one: VIMZ_ERR_INVALID).  acc_out
  * (optional): the accumulator of the LAST chunk, next_pow2(max(n_c, n_w)) elements.
  * _batch_scalars: the two entry points with GIVEN multipliers, 6 of 2 words a proof (the openings of its BN254 arguments in order, W before E, then those of its
- * Grumpkin arguments; the unused ones must be non-zero too).  Whoever knows the multipliers can make a chunk of wrong proofs pass. */
+ * Grumpkin arguments; the unused ones must be non-zero too).  Whoever knows the multipliers can make a chunk of wrong proofs pass.
+ * The _ex twins of _instance_batch and _batch_scalars add flags, leaf and stats[4] as the _ex entry points take them (include/vimz_hip.h); acc_out stays the
+ * accumulator of the last chunk's FULL equation, not of a subset. */
 int vimz_test_spartan_batch_group(void);
 int vimz_test_spartan_batch_split(void);
 int vimz_test_spartan_mat_eval(vimz_ctx* ctx, int curve, size_t n_c, size_t n_w, const vimz_coo* A, const vimz_coo* B, const vimz_coo* C, size_t n, const uint64_t* rx,
@@ -300,8 +306,28 @@ int vimz_test_spartan_instance_batch(vimz_ctx* ctx, int curve, size_t n_c, size_
                                      uint64_t* acc_out);
 int vimz_testing_ivc_verify_compressed_batch_scalars(vimz_ivc* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0,
                                                      size_t chunk, const uint64_t* multipliers, uint32_t* results, double seconds[6]);
+int vimz_test_spartan_instance_batch_ex(vimz_ctx* ctx, int curve, size_t n_c, size_t n_w, uint32_t n_pub, const vimz_coo* A, const vimz_coo* B, const vimz_coo* C,
+                                        const vimz_bases* ck, const uint64_t digest[4], uint32_t side_tag, const char* label, size_t n, const uint64_t* inst, const int* has_E,
+                                        const uint64_t* const* words, const size_t* n_words, size_t chunk, const uint64_t* multipliers, uint32_t* results, double seconds[6],
+                                        uint64_t* acc_out, uint32_t flags, size_t leaf, uint64_t stats[4]);
+int vimz_testing_ivc_verify_batch_compressed_scalars_ex(vimz_ivc* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0,
+                                                        size_t chunk, const uint64_t* multipliers, uint32_t* results, double seconds[6], uint32_t flags, size_t leaf,
+                                                        uint64_t stats[4]);
+int vimz_testing_cf_verify_batch_compressed_scalars_ex(vimz_cf* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0,
+                                                       size_t chunk, const uint64_t* multipliers, uint32_t* results, double seconds[6], uint32_t flags, size_t leaf,
+                                                       uint64_t stats[4]);
 int vimz_testing_cf_verify_compressed_batch_scalars(vimz_cf* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0,
                                                     size_t chunk, const uint64_t* multipliers, uint32_t* results, double seconds[6]);
+int vimz_test_spartan_instance_batch_ex(vimz_ctx* ctx, int curve, size_t n_c, size_t n_w, uint32_t n_pub, const vimz_coo* A, const vimz_coo* B, const vimz_coo* C,
+                                        const vimz_bases* ck, const uint64_t digest[4], uint32_t side_tag, const char* label, size_t n, const uint64_t* inst, const int* has_E,
+                                        const uint64_t* const* words, const size_t* n_words, size_t chunk, const uint64_t* multipliers, uint32_t* results, double seconds[6],
+                                        uint64_t* acc_out, uint32_t flags, size_t leaf, uint64_t stats[4]);
+int vimz_testing_ivc_verify_batch_compressed_scalars_ex(vimz_ivc* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0,
+                                                        size_t chunk, const uint64_t* multipliers, uint32_t* results, double seconds[6], uint32_t flags, size_t leaf,
+                                                        uint64_t stats[4]);
+int vimz_testing_cf_verify_batch_compressed_scalars_ex(vimz_cf* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0,
+                                                       size_t chunk, const uint64_t* multipliers, uint32_t* results, double seconds[6], uint32_t flags, size_t leaf,
+                                                       uint64_t stats[4]);
 
 /* The device's square root over Fq2 (vimz_amd/csrc/g16_point_pack.hpp: fq2_sqrt), one thread per value (tests/test_gpu_point_pack.py): values: n elements of Fq2,
  * c0 then c1, canonical, 4 words each (one not below q: VIMZ_ERR_INVALID); roots_out: the same layout, is_square_out[i] = 1 when roots_out[i] squares to values[i],

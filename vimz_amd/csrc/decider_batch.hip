@@ -88,6 +88,18 @@ struct DeviceStages : Stages {
     wipe();
     return ok;
   }
+  // (no multiplier is uploaded here: the plan names rows, the rows are points)
+  bool subset_sums(size_t m, const ColsumPlan& plan, G1A* sums) override {
+    if (!d_rows || m != rows_m || plan.n_points != (size_t)ROWS * m) { err = hipErrorInvalidValue; what = "subset sums before the rows"; return false; }
+    Buf dsums;
+    struct Plan { ColsumDevice d; ~Plan() { g16_colsum_free(d); } } P;
+    DB_TRY(dsums.alloc(sizeof(G1A) * plan.n_cols));
+    DB_TRY(g16_colsum_upload(plan, sizeof(G1A), &P.d));
+    DB_TRY(g16_column_sums(s, P.d, (const G1Aff*)d_rows, (G1Aff*)dsums.p));
+    DB_TRY(hipMemcpyAsync(sums, dsums.p, sizeof(G1A) * plan.n_cols, hipMemcpyDeviceToHost, s));
+    DB_TRY(hipStreamSynchronize(s));
+    return true;
+  }
   bool miller(size_t m, const G2A* B, Fq12* out) override {
     if (!d_rows || m != rows_m) { err = hipErrorInvalidValue; what = "the Miller stage before the rows"; return false; }
     Buf dq, dout;
@@ -104,7 +116,7 @@ struct DeviceStages : Stages {
 unsigned batch_threads() { return std::max(1u, std::min(16u, usable_cpus())); }      // as the decider's host code sizes its pools (g16_powers_verify.hip: points_in)
 
 int batch_entry(const char* name, vimz_ctx* ctx, const uint64_t* key_words, size_t n_key_words, uint32_t len_z, size_t n, const uint64_t* steps, const uint64_t* z0, const uint64_t* zi,
-                const uint64_t* words, size_t chunk, const uint64_t* given, uint32_t* results, double seconds[6]) {
+                const uint64_t* words, size_t chunk, const uint64_t* given, uint32_t* results, double seconds[6], uint32_t flags, size_t leaf, uint64_t* stats) {
   auto bad = [&](const char* why) { const std::string m = std::string(name) + ": " + why; return vz_fail(ctx, VIMZ_ERR_INVALID, m.c_str()); };
   if (!key_words) return bad("NULL key");
   if (n && (!steps || !z0 || !zi || !words || !results)) return bad("NULL argument");
@@ -112,14 +124,16 @@ int batch_entry(const char* name, vimz_ctx* ctx, const uint64_t* key_words, size
   VerifierKey K;
   if (!parse_key(key_words, n_key_words, &K)) return bad("malformed key");
   if (K.len_z != len_z) return bad("len_z disagrees with the key");
+  if (flags & ~BATCH_NO_BISECT) return bad("unknown flag");
   if (!chunk) chunk = DEFAULT_CHUNK;
+  if (!leaf) leaf = ctx ? DEFAULT_LEAF : DEFAULT_LEAF_HOST;
   int rc;
-  if (!ctx) { HostStages st(batch_threads()); rc = verify_batch(K, n, steps, z0, zi, words, chunk, given, st, batch_threads(), results, seconds); }
+  if (!ctx) { HostStages st(batch_threads()); rc = verify_batch(K, n, steps, z0, zi, words, chunk, given, st, batch_threads(), results, seconds, flags, leaf, stats); }
   else {
     std::lock_guard<std::mutex> g(ctx->mu);
     P_TRY(hipSetDevice(ctx->device));
     DeviceStages st(ctx);
-    rc = verify_batch(K, n, steps, z0, zi, words, chunk, given, st, batch_threads(), results, seconds);
+    rc = verify_batch(K, n, steps, z0, zi, words, chunk, given, st, batch_threads(), results, seconds, flags, leaf, stats);
     if (rc == BATCH_STAGE_FAILED) return vz_fail(ctx, VIMZ_ERR_HIP, st.what, st.err);
   }
   switch (rc) {
@@ -135,14 +149,25 @@ int batch_entry(const char* name, vimz_ctx* ctx, const uint64_t* key_words, size
 
 extern "C" int vimz_decider_verify_batch(vimz_ctx* ctx, const uint64_t* key_words, size_t n_key_words, uint32_t len_z, size_t n, const uint64_t* steps, const uint64_t* z0,
                                          const uint64_t* zi, const uint64_t* words, size_t chunk, uint32_t* results, double seconds[6]) {
-  return batch_entry("vimz_decider_verify_batch", ctx, key_words, n_key_words, len_z, n, steps, z0, zi, words, chunk, nullptr, results, seconds);
+  return vimz_decider_verify_batch_ex(ctx, key_words, n_key_words, len_z, n, steps, z0, zi, words, chunk, results, seconds, 0, 0, nullptr);
+}
+extern "C" int vimz_decider_verify_batch_ex(vimz_ctx* ctx, const uint64_t* key_words, size_t n_key_words, uint32_t len_z, size_t n, const uint64_t* steps, const uint64_t* z0,
+                                            const uint64_t* zi, const uint64_t* words, size_t chunk, uint32_t* results, double seconds[6], uint32_t flags, size_t leaf,
+                                            uint64_t stats[4]) {
+  return batch_entry("vimz_decider_verify_batch", ctx, key_words, n_key_words, len_z, n, steps, z0, zi, words, chunk, nullptr, results, seconds, flags, leaf, stats);
 }
 
 #ifdef VIMZ_TESTING
 extern "C" int vimz_testing_decider_verify_batch_scalars(vimz_ctx* ctx, const uint64_t* key_words, size_t n_key_words, uint32_t len_z, size_t n, const uint64_t* steps, const uint64_t* z0,
                                                          const uint64_t* zi, const uint64_t* words, size_t chunk, const uint64_t* multipliers, uint32_t* results, double seconds[6]) {
+  return vimz_testing_decider_verify_batch_scalars_ex(ctx, key_words, n_key_words, len_z, n, steps, z0, zi, words, chunk, multipliers, results, seconds, 0, 0, nullptr);
+}
+extern "C" int vimz_testing_decider_verify_batch_scalars_ex(vimz_ctx* ctx, const uint64_t* key_words, size_t n_key_words, uint32_t len_z, size_t n, const uint64_t* steps,
+                                                            const uint64_t* z0, const uint64_t* zi, const uint64_t* words, size_t chunk, const uint64_t* multipliers,
+                                                            uint32_t* results, double seconds[6], uint32_t flags, size_t leaf, uint64_t stats[4]) {
   if (n && !multipliers) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_testing_decider_verify_batch_scalars: NULL multipliers");
-  return batch_entry("vimz_testing_decider_verify_batch_scalars", ctx, key_words, n_key_words, len_z, n, steps, z0, zi, words, chunk, multipliers, results, seconds);
+  return batch_entry("vimz_testing_decider_verify_batch_scalars", ctx, key_words, n_key_words, len_z, n, steps, z0, zi, words, chunk, multipliers, results, seconds, flags, leaf,
+                     stats);
 }
 
 extern "C" int vimz_test_miller_loops(vimz_ctx* ctx, const uint64_t* g1_xy, const uint64_t* g2_xy, size_t n, uint32_t* out) {

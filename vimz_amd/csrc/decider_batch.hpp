@@ -8,19 +8,25 @@
 // is one after ONE final exponentiation: the 3·|S| equations of the single verifier (decider_verify.hpp: verify_words) in a random combination, wrong with probability
 // about 2^-128 when one of them fails.  What every proof brings of its own is B_i, so one Miller loop a proof remains; B_i enters only after it has passed "on the
 // twist" and r·B_i = O BY ITSELF — a sum cannot see a component in the twist's small cofactor subgroups (g16_powers_verify.hip says the same of a string's points).
-// An accepted chunk gives its members their DV_STEPS bit; a refused chunk is judged member by member by verify_words, which gives the exact bits with no second
-// implementation of them.  There is no bisection: one bad proof costs its chunk |S| single verifications.
+// An accepted chunk gives its members their DV_STEPS bit.  A refused chunk is BISECTED (batch_bisect.hpp): the same equation is asked of halves, every member
+// under the multipliers it had, from the rows and Miller values that are already there — a subset costs its column sums (one device pass a level, over all refused
+// chunks), the product of its Miller values, the five fixed-G2 loops and one final exponentiation, and the subsets of a level are judged side by side on the
+// host's threads.  A member is accepted only inside a subset whose equation was evaluated and held; a refused subset of at most `leaf` members is judged member by
+// member by verify_words, which gives the exact bits with no second implementation of them.  At most 2·(|S| − 1) subsets are asked of a refused chunk S.
+// BATCH_NO_BISECT sends a refused chunk to verify_words whole (|S| single verifications).  profiles/batch_bisect.txt has the measured costs behind DEFAULT_LEAF.
 //
 // Stages (what `Stages` abstracts; one thread an element in each):
 //   point_flags   pt_flags over the 8 G1 points and the B of every proof the parse let through
 //   lincomb       ROWS rows a proof of out = a + k·b (g1_lincomb_thread) — the folded commitments, −rho·A, rho·C and the eight KZG terms —, the folded commitments back
-//                 to the host (it needs their limbs), the other rows summed per chunk by colsum_run over batch_sum_plan's plan
+//                 to the host (it needs their limbs), the other rows summed per chunk by colsum_run over batch_sum_plan's plan; the rows stay where they are
+//   subset_sums   the same three column sums over any list of ranges of the resident rows (range_sum_plan): what a bisection level asks
 //   miller        miller_thread over (−rho_i·A_i, B_i)
 #pragma once
 #include <sys/random.h>
 #include <chrono>
 #include <functional>
 #include <thread>
+#include "batch_bisect.hpp"
 #include "decider_verify.hpp"
 #include "pairing_stage.hpp"
 
@@ -30,23 +36,35 @@ namespace dvb {
 using namespace dv;
 using pairing::Fq12;
 
-constexpr size_t DEFAULT_CHUNK = 256;      // one refused chunk costs the fallback 256 single verifications (0.03 s each, over the threads): about half a second
+constexpr size_t DEFAULT_CHUNK = 256;      // (a refused chunk without bisection: 256 single verifications of 0.03 s each, over the threads — about half a second)
+// the default leaf: the smallest power of two >= 8·kappa, kappa = (one subset evaluation at chunk/2) / (a single verification as the fallback schedules it, 1.87 ms
+// over 16 threads).  Measured (profiles/batch_bisect.txt): 20.9 ms an evaluation on the device path (kappa 11.2), 13.3 ms on the host path (kappa 7.1)
+constexpr size_t DEFAULT_LEAF = 128, DEFAULT_LEAF_HOST = 64;
+constexpr uint32_t BATCH_NO_BISECT = 1;    // flags bit 0 (VIMZ_BATCH_NO_BISECT)
 constexpr uint32_t MULT_BITS = 128, FULL_BITS = 254;
 // the rows of one proof; row `kind` of survivor j is element kind·m + j of the arrays (a kind's rows side by side: the Miller stage reads kind R_NA as its P)
 enum { R_CMW = 0, R_CME, R_NA, R_RC, R_SPIW, R_SPIE, R_XPIW, R_XPIE, R_SUW, R_SLW, R_SUE, R_ST, ROWS };
 constexpr uint32_t SUMS = 3;               // columns a chunk: Σ rho·C;  the G1 side of the VK pairing;  that of the G_2 pairing before y·G_1
 inline uint32_t row_column(int kind) { return kind == R_RC ? 0u : kind <= R_SPIE ? 1u : 2u; }
 
-// the plan (g16_colsum_plan.hpp) of the per-chunk sums over the ROWS·m rows of m proofs cut into chunks of `chunk`: column SUMS·c + s takes the rows of its kind of
-// chunk c's members, coefficient one.  The rows R_CMW, R_CME, R_NA are in no column.
-inline bool batch_sum_plan(size_t m, size_t chunk, ColsumPlan* plan) {
-  if (!m || !chunk || m >= ((size_t)1 << 26)) return false;
-  const size_t n_chunks = (m + chunk - 1) / chunk;
+// the plan (g16_colsum_plan.hpp) of the sums over the ROWS·m rows of m proofs for a list of ranges [lo, hi) of them: column SUMS·r + s takes the rows of its kind
+// of range r's members, coefficient one.  The rows R_CMW, R_CME, R_NA are in no column.  Ranges may be any (a bisection level's are disjoint); an empty list is refused.
+inline bool range_sum_plan(size_t m, const bb::Subset* ranges, size_t n_ranges, ColsumPlan* plan) {
+  if (!m || !n_ranges || m >= ((size_t)1 << 26) || n_ranges >= ((size_t)1 << 26)) return false;
   std::vector<ColsumUnit> units;
-  units.reserve((ROWS - R_RC) * m);
-  for (int kind = R_RC; kind < ROWS; kind++)
-    for (size_t j = 0; j < m; j++) units.push_back({(uint32_t)(kind * m + j), (uint32_t)(SUMS * (j / chunk) + row_column(kind))});
-  return colsum_plan(nullptr, 0, units.data(), units.size(), nullptr, 0, BnFr::MOD.w, (uint32_t)(SUMS * n_chunks), (uint32_t)(ROWS * m), plan, nullptr);
+  for (size_t r = 0; r < n_ranges; r++) {
+    if (ranges[r].lo >= ranges[r].hi || ranges[r].hi > m) return false;
+    for (int kind = R_RC; kind < ROWS; kind++)
+      for (size_t j = ranges[r].lo; j < ranges[r].hi; j++) units.push_back({(uint32_t)(kind * m + j), (uint32_t)(SUMS * r + row_column(kind))});
+  }
+  return colsum_plan(nullptr, 0, units.data(), units.size(), nullptr, 0, BnFr::MOD.w, (uint32_t)(SUMS * n_ranges), (uint32_t)(ROWS * m), plan, nullptr);
+}
+// the per-chunk sums of m proofs cut into chunks of `chunk`: the ranges are the chunks
+inline bool batch_sum_plan(size_t m, size_t chunk, ColsumPlan* plan) {
+  if (!m || !chunk) return false;
+  std::vector<bb::Subset> ranges;
+  for (size_t lo = 0; lo < m; lo += chunk) ranges.push_back({lo, std::min(m, lo + chunk), 1u});
+  return range_sum_plan(m, ranges.data(), ranges.size(), plan);
 }
 
 struct Stages {
@@ -57,6 +75,8 @@ struct Stages {
   virtual bool lincomb(size_t m, const G1A* a, const uint32_t* k, const uint32_t* bits, const G1A* b, const ColsumPlan& plan, G1A* cm, G1A* sums) = 0;
   // out[j] = the Miller value of (rows[R_NA·m + j], B[j])
   virtual bool miller(size_t m, const G2A* B, Fq12* out) = 0;
+  // sums <- the columns of a plan of range_sum_plan over the rows lincomb left (m: as lincomb's)
+  virtual bool subset_sums(size_t m, const ColsumPlan& plan, G1A* sums) = 0;
 };
 
 // fn(lo, hi) over [0, n) on up to `threads` threads
@@ -83,6 +103,10 @@ struct HostStages : Stages {
     rows.assign(ROWS * m, G1A());
     parallel_for(ROWS * m, threads, [&](size_t lo, size_t hi) { for (size_t t = lo; t < hi; t++) pairing::g1_lincomb_thread(t, a, k, bits, b, rows.data()); });
     memcpy((void*)cm, (const void*)rows.data(), sizeof(G1A) * 2 * m);
+    return subset_sums(m, plan, sums);
+  }
+  bool subset_sums(size_t m, const ColsumPlan& plan, G1A* sums) override {
+    if (rows.size() != ROWS * m || plan.n_points != ROWS * m) return false;
     memset((void*)sums, 0, sizeof(G1A) * plan.n_cols);
     std::vector<G1A> partials[2];
     for (size_t lv = 0; lv < plan.levels.size(); lv++) {
@@ -127,9 +151,13 @@ enum { BATCH_OK = 0, BATCH_NO_RANDOMNESS = 1, BATCH_ZERO_MULTIPLIER = 2, BATCH_S
 
 // results[i] = what verify_words gives for proof i alone.  steps: n; z0, zi: n·len_z·4 words; words: n·100.  chunk >= 1.  given: NULL — the multipliers are drawn
 // from the OS — or 3n multipliers of 2 words (rho_i, sigma_i, sigma'_i of proof i; a test's: with known multipliers a chunk can be forged).  seconds[6] (optional):
-// parse + per-proof host work, per-proof stage, Miller loops, host sums + fixed-G2 loops + final exponentiations, fallback, total.
+// parse + per-proof host work, per-proof stage, Miller loops, host sums + fixed-G2 loops + final exponentiations, fallback (the subset equations of refused chunks
+// and the single verifications), total.  flags: BATCH_NO_BISECT.  leaf >= 1.  stats[4] (optional): chunks refused, subset equations evaluated after a refusal,
+// single verifications run, members of refused chunks accepted by a subset equation.
 inline int verify_batch(const VerifierKey& K, size_t n, const uint64_t* steps, const uint64_t* z0, const uint64_t* zi, const uint64_t* words, size_t chunk,
-                        const uint64_t* given, Stages& st, unsigned threads, uint32_t* results, double* seconds) {
+                        const uint64_t* given, Stages& st, unsigned threads, uint32_t* results, double* seconds, uint32_t flags = 0, size_t leaf = DEFAULT_LEAF,
+                        uint64_t* stats = nullptr) {
+  if (stats) memset(stats, 0, 8 * bb::ST_N);
   const auto t_all = std::chrono::steady_clock::now();
   double sec[6] = {0, 0, 0, 0, 0, 0};
   auto done = [&](int rc) { sec[5] = since(t_all); if (seconds) memcpy(seconds, sec, sizeof(sec)); return rc; };
@@ -232,49 +260,68 @@ inline int verify_batch(const VerifierKey& K, size_t n, const uint64_t* steps, c
   sec[0] += since(t0);
   t0 = std::chrono::steady_clock::now();
   const size_t n_pub = K.ic.size() - 1;
+  // the equation over the members [lo, hi) with their three column sums: the chunks' body, and a bisection's subsets'
+  auto judge = [&](size_t lo, size_t hi, const G1A* sum3) {
+    Fr rho_sum = Fr::zero(), y_sum = Fr::zero();
+    std::vector<Fr> pub_sum(n_pub, Fr::zero());
+    Fq12 f = Fq12::one();
+    for (size_t j = lo; j < hi; j++) {
+      const Proof& p = proofs[idx[j]]; const uint64_t* w = w_of(idx[j]);
+      Fr rho = Fr::to_mont(fr_of_words(&S.mult[6 * j], 2));
+      rho_sum = Fr::add(rho_sum, rho);
+      for (size_t k = 0; k < n_pub; k++) pub_sum[k] = Fr::add(pub_sum[k], Fr::mul(rho, p.pub[k]));
+      for (int e = 0; e < 2; e++) {
+        Fr sm = Fr::to_mont(fr_of_words(&S.mult[6 * j + 2 + 2 * e], 2));
+        y_sum = Fr::add(y_sum, Fr::mul(sm, Fr::to_mont(fr_of_words(w + 4 * (19 + e), 4))));
+        explicit_bzero(&sm, sizeof(sm));
+      }
+      explicit_bzero(&rho, sizeof(rho));
+      f = Fq12::mul(f, mv[j]);
+    }
+    auto mul = [](const G1A& p, const Fr& k_mont) { const Fr c = Fr::from_mont(k_mont); return pt_scalar_mul(p, c.v); };
+    G1X vkx = mul(K.ic[0], rho_sum);
+    for (size_t k = 0; k < n_pub; k++) { if (pub_sum[k].is_zero() || aff_is_identity(K.ic[k + 1])) continue; const G1X t = mul(K.ic[k + 1], pub_sum[k]); add_full(vkx, t); }
+    G1X g2side = mul(K.kzg_g1, y_sum);
+    add_mixed(g2side, sum3[2]);
+    f = Fq12::mul(f, miller_one(to_affine(mul(K.alpha, rho_sum)), K.beta));
+    f = Fq12::mul(f, miller_one(to_affine(vkx), K.gamma));
+    f = Fq12::mul(f, miller_one(sum3[0], K.delta));
+    f = Fq12::mul(f, miller_one(sum3[1], K.kzg_vk));
+    f = Fq12::mul(f, miller_one(to_affine(g2side), K.kzg_g2));
+    const bool ok = pairing::fq12_pow(f, pairing::consts().final_exp).is_one();
+    explicit_bzero(&rho_sum, sizeof(rho_sum)); explicit_bzero(&y_sum, sizeof(y_sum));
+    if (n_pub) explicit_bzero((void*)pub_sum.data(), sizeof(Fr) * n_pub);
+    return ok;
+  };
   std::vector<uint8_t> accepted(n_chunks, 0);
   parallel_for(n_chunks, threads, [&](size_t clo, size_t chi) {
-    for (size_t c = clo; c < chi; c++) {
-      const size_t lo = c * chunk, hi = std::min(m, lo + chunk);
-      Fr rho_sum = Fr::zero(), y_sum = Fr::zero();
-      std::vector<Fr> pub_sum(n_pub, Fr::zero());
-      Fq12 f = Fq12::one();
-      for (size_t j = lo; j < hi; j++) {
-        const Proof& p = proofs[idx[j]]; const uint64_t* w = w_of(idx[j]);
-        Fr rho = Fr::to_mont(fr_of_words(&S.mult[6 * j], 2));
-        rho_sum = Fr::add(rho_sum, rho);
-        for (size_t k = 0; k < n_pub; k++) pub_sum[k] = Fr::add(pub_sum[k], Fr::mul(rho, p.pub[k]));
-        for (int e = 0; e < 2; e++) {
-          Fr sm = Fr::to_mont(fr_of_words(&S.mult[6 * j + 2 + 2 * e], 2));
-          y_sum = Fr::add(y_sum, Fr::mul(sm, Fr::to_mont(fr_of_words(w + 4 * (19 + e), 4))));
-          explicit_bzero(&sm, sizeof(sm));
-        }
-        explicit_bzero(&rho, sizeof(rho));
-        f = Fq12::mul(f, mv[j]);
-      }
-      auto mul = [](const G1A& p, const Fr& k_mont) { const Fr c = Fr::from_mont(k_mont); return pt_scalar_mul(p, c.v); };
-      G1X vkx = mul(K.ic[0], rho_sum);
-      for (size_t k = 0; k < n_pub; k++) { if (pub_sum[k].is_zero() || aff_is_identity(K.ic[k + 1])) continue; const G1X t = mul(K.ic[k + 1], pub_sum[k]); add_full(vkx, t); }
-      G1X g2side = mul(K.kzg_g1, y_sum);
-      add_mixed(g2side, sums[SUMS * c + 2]);
-      f = Fq12::mul(f, miller_one(to_affine(mul(K.alpha, rho_sum)), K.beta));
-      f = Fq12::mul(f, miller_one(to_affine(vkx), K.gamma));
-      f = Fq12::mul(f, miller_one(sums[SUMS * c + 0], K.delta));
-      f = Fq12::mul(f, miller_one(sums[SUMS * c + 1], K.kzg_vk));
-      f = Fq12::mul(f, miller_one(to_affine(g2side), K.kzg_g2));
-      accepted[c] = pairing::fq12_pow(f, pairing::consts().final_exp).is_one() ? 1 : 0;
-      explicit_bzero(&rho_sum, sizeof(rho_sum));
-    }
+    for (size_t c = clo; c < chi; c++) accepted[c] = judge(c * chunk, std::min(m, c * chunk + chunk), &sums[SUMS * c]) ? 1 : 0;
   });
   sec[3] += since(t0);
 
-  // 6. a refused chunk member by member (an accepted member keeps its DV_STEPS bit)
+  // 6. a refused chunk: bisected over the rows and Miller values that are there, its refused leaves member by member (an accepted member keeps its DV_STEPS bit)
   t0 = std::chrono::steady_clock::now();
+  std::vector<bb::Subset> roots;
+  for (size_t c = 0; c < n_chunks; c++) if (!accepted[c]) roots.push_back({c * chunk, std::min(m, c * chunk + chunk), 1u});
+  bb::Outcome out;
+  if (flags & BATCH_NO_BISECT) { out.singles = roots; }
+  else {
+    const bool ok = bb::bisect(roots, leaf, [&](const std::vector<bb::Subset>& ask, std::vector<uint32_t>& held) {
+      ColsumPlan sub;
+      if (!range_sum_plan(m, ask.data(), ask.size(), &sub)) return false;
+      std::vector<G1A> ss(SUMS * ask.size());
+      if (!st.subset_sums(m, sub, ss.data())) return false;
+      parallel_for(ask.size(), threads, [&](size_t lo, size_t hi) { for (size_t k = lo; k < hi; k++) held[k] = judge(ask[k].lo, ask[k].hi, &ss[SUMS * k]) ? 1u : 0u; });
+      return true;
+    }, &out);
+    if (!ok) return done(BATCH_STAGE_FAILED);
+  }
   std::vector<size_t> again;
-  for (size_t j = 0; j < m; j++) if (!accepted[j / chunk]) again.push_back(idx[j]);
+  for (const bb::Subset& sgl : out.singles) for (size_t j = sgl.lo; j < sgl.hi; j++) again.push_back(idx[j]);
   parallel_for(again.size(), threads, [&](size_t lo, size_t hi) {
     for (size_t q = lo; q < hi; q++) { const size_t i = again[q]; results[i] = verify_words(K, steps[i], z0_of(i), zi_of(i), w_of(i)); }
   });
+  if (stats) { stats[bb::ST_REFUSED] = roots.size(); stats[bb::ST_EQUATIONS] = out.equations; stats[bb::ST_SINGLES] = again.size(); stats[bb::ST_ACCEPTED] = out.accepted; }
   sec[4] += since(t0);
   return done(BATCH_OK);
 }

@@ -1217,7 +1217,7 @@ namespace {
 uint64_t first_word(const uint8_t* blob, size_t len) { uint64_t w = 0; if (blob && len >= 8) memcpy(&w, blob, 8); return w; }
 
 int ivc_compressed_batch(const char* who, vimz_ivc* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0, size_t chunk,
-                         const uint64_t* given, uint32_t* results, double seconds[6], BatchProbe* probe) {
+                         const uint64_t* given, uint32_t* results, double seconds[6], BatchProbe* probe, uint32_t flags, size_t leaf, uint64_t* stats) {
   if (!vk) return VIMZ_ERR_INVALID;
   vimz_ctx* ctx = vk->ctx;
   if (n && (!blobs || !lens || !steps || !z0 || !results)) return vz_fail(ctx, VIMZ_ERR_INVALID, "compressed batch: NULL argument");
@@ -1237,11 +1237,11 @@ int ivc_compressed_batch(const char* who, vimz_ivc* vk, size_t n, const uint8_t*
     }
   };
   return compressed_batch(who, ctx, cache, vk->ck1, vk->ck2, n, chunk, given, [&](size_t i, DeferredVerify& vf, uint32_t* res) { return run(vf, i, res); },
-                          [&](size_t i, uint32_t* res) { SingleVerify vf; return run(vf, i, res); }, results, seconds, probe);
+                          [&](size_t i, uint32_t* res) { SingleVerify vf; return run(vf, i, res); }, results, seconds, probe, flags, leaf, stats);
 }
 
 int cf_compressed_batch(const char* who, vimz_cf* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0, size_t chunk,
-                        const uint64_t* given, uint32_t* results, double seconds[6], BatchProbe* probe) {
+                        const uint64_t* given, uint32_t* results, double seconds[6], BatchProbe* probe, uint32_t flags, size_t leaf, uint64_t* stats) {
   if (!vk) return VIMZ_ERR_INVALID;
   vimz_ctx* ctx = vk->ctx;
   if (n && (!blobs || !lens || !steps || !z0 || !results)) return vz_fail(ctx, VIMZ_ERR_INVALID, "compressed batch: NULL argument");
@@ -1261,7 +1261,7 @@ int cf_compressed_batch(const char* who, vimz_cf* vk, size_t n, const uint8_t* c
     }
   };
   return compressed_batch(who, ctx, cache, vk->ck1, vk->ck2, n, chunk, given, [&](size_t i, DeferredVerify& vf, uint32_t* res) { return run(vf, i, res); },
-                          [&](size_t i, uint32_t* res) { SingleVerify vf; return run(vf, i, res); }, results, seconds, probe);
+                          [&](size_t i, uint32_t* res) { SingleVerify vf; return run(vf, i, res); }, results, seconds, probe, flags, leaf, stats);
 }
 }  // namespace
 
@@ -1270,16 +1270,24 @@ extern "C" {
 // Many compressed proofs under one verifier key in one call.  blobs[i] / lens[i]: what vimz_ivc_compress or vimz_ivc_merged_compress wrote (the first word tells
 // which; the two kinds may be mixed; anything else — a Nova + CycleFold blob among them — gets bit 13); steps[i] and z0 + 4·len_z·i: the statement of proof i.
 // results[i] = the word vimz_ivc_verify_compressed / vimz_ivc_verify_merged_compressed gives for proof i alone.  chunk: proofs an equation (0 = 32); a refused
-// chunk is judged member by member by the single verifier (spartan_batch.hpp).  n = 0 is accepted.  seconds[6] (optional): parse + host checks, half-tables,
-// matrix evaluation, s-vector accumulation, MSMs, fallback.
+// chunk is bisected down to refused subsets of `leaf` members, which the single verifier judges member by member (spartan_batch.hpp).  n = 0 is accepted.
+// seconds[6] (optional): parse + host checks, half-tables, matrix evaluation, s-vector accumulation, MSMs, fallback.  flags, leaf, stats: include/vimz_hip.h.
 int vimz_ivc_verify_compressed_batch(vimz_ivc* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0, size_t chunk,
                                      uint32_t* results, double seconds[6]) {
-  return ivc_compressed_batch("vimz_ivc_verify_compressed_batch", vk, n, blobs, lens, steps, z0, chunk, nullptr, results, seconds, nullptr);
+  return vimz_ivc_verify_batch_compressed_ex(vk, n, blobs, lens, steps, z0, chunk, results, seconds, 0, 0, nullptr);
+}
+int vimz_ivc_verify_batch_compressed_ex(vimz_ivc* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0, size_t chunk,
+                                        uint32_t* results, double seconds[6], uint32_t flags, size_t leaf, uint64_t stats[4]) {
+  return ivc_compressed_batch("vimz_ivc_verify_compressed_batch", vk, n, blobs, lens, steps, z0, chunk, nullptr, results, seconds, nullptr, flags, leaf, stats);
 }
 // The same for what vimz_cf_compress / vimz_cf_merged_compress wrote; results[i] = vimz_cf_verify_compressed's / vimz_cf_verify_merged_compressed's word.
 int vimz_cf_verify_compressed_batch(vimz_cf* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0, size_t chunk,
                                     uint32_t* results, double seconds[6]) {
-  return cf_compressed_batch("vimz_cf_verify_compressed_batch", vk, n, blobs, lens, steps, z0, chunk, nullptr, results, seconds, nullptr);
+  return vimz_cf_verify_batch_compressed_ex(vk, n, blobs, lens, steps, z0, chunk, results, seconds, 0, 0, nullptr);
+}
+int vimz_cf_verify_batch_compressed_ex(vimz_cf* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0, size_t chunk,
+                                       uint32_t* results, double seconds[6], uint32_t flags, size_t leaf, uint64_t stats[4]) {
+  return cf_compressed_batch("vimz_cf_verify_compressed_batch", vk, n, blobs, lens, steps, z0, chunk, nullptr, results, seconds, nullptr, flags, leaf, stats);
 }
 
 }  // extern "C"
@@ -1632,7 +1640,7 @@ int test_instance_word(V& vf, vimz_ctx* ctx, TestSide& T, SideDev& S, const Test
 template <class F, class C>
 int test_instance_batch(vimz_ctx* ctx, int curve, const vimz_r1cs* R, const vimz_bases* ck, const uint64_t digest[4], uint32_t side_tag, const char* label, uint32_t n_pub,
                         size_t n, const uint64_t* inst, const int* has_E, const uint64_t* const* words, const size_t* n_words, size_t chunk, const uint64_t* multipliers,
-                        uint32_t* results, double seconds[6], uint64_t* acc_out) {
+                        uint32_t* results, double seconds[6], uint64_t* acc_out, uint32_t flags, size_t leaf, uint64_t* stats) {
   typedef typename C::Base FS;
   std::vector<F> dg;
   if (!canon_in(digest, 1, dg)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_instance_batch: element not below the modulus");
@@ -1663,7 +1671,7 @@ int test_instance_batch(vimz_ctx* ctx, int curve, const vimz_r1cs* R, const vimz
   };
   return compressed_batch("vimz_test_spartan_instance_batch", ctx, &T.cache, ck, ck, n, chunk, multipliers ? given.data() : nullptr,
                           [&](size_t i, DeferredVerify& vf, uint32_t* res) { return run(vf, i, res); },
-                          [&](size_t i, uint32_t* res) { SingleVerify vf; return run(vf, i, res); }, results, seconds, acc_out ? &probe : nullptr);
+                          [&](size_t i, uint32_t* res) { SingleVerify vf; return run(vf, i, res); }, results, seconds, acc_out ? &probe : nullptr, flags, leaf, stats);
 }
 
 }  // namespace
@@ -1699,25 +1707,42 @@ int vimz_test_spartan_instance_batch(vimz_ctx* ctx, int curve, size_t n_c, size_
                                      const vimz_bases* ck, const uint64_t digest[4], uint32_t side_tag, const char* label, size_t n, const uint64_t* inst, const int* has_E,
                                      const uint64_t* const* words, const size_t* n_words, size_t chunk, const uint64_t* multipliers, uint32_t* results, double seconds[6],
                                      uint64_t* acc_out) {
+  return vimz_test_spartan_instance_batch_ex(ctx, curve, n_c, n_w, n_pub, A, B, C, ck, digest, side_tag, label, n, inst, has_E, words, n_words, chunk, multipliers, results, seconds,
+                                             acc_out, 0, 0, nullptr);
+}
+int vimz_test_spartan_instance_batch_ex(vimz_ctx* ctx, int curve, size_t n_c, size_t n_w, uint32_t n_pub, const vimz_coo* A, const vimz_coo* B, const vimz_coo* C,
+                                        const vimz_bases* ck, const uint64_t digest[4], uint32_t side_tag, const char* label, size_t n, const uint64_t* inst, const int* has_E,
+                                        const uint64_t* const* words, const size_t* n_words, size_t chunk, const uint64_t* multipliers, uint32_t* results, double seconds[6],
+                                        uint64_t* acc_out, uint32_t flags, size_t leaf, uint64_t stats[4]) {
   if (!ctx || !A || !B || !C || !ck || !digest || !label || (n && (!inst || !has_E || !words || !n_words || !results)))
     return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_instance_batch: bad argument");
   for (size_t i = 0; i < n; i++) if (!words[i] && n_words[i]) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_spartan_instance_batch: bad argument");
   return (int)instance_dispatch(ctx, curve, n_c, n_w, n_pub, A, B, C, ck, "vimz_test_spartan_instance_batch: bad argument", [&](const vimz_r1cs* R) -> int64_t {
     return curve == VIMZ_CURVE_BN254_G1
-             ? test_instance_batch<Fe, BnG1>(ctx, curve, R, ck, digest, side_tag, label, n_pub, n, inst, has_E, words, n_words, chunk, multipliers, results, seconds, acc_out)
-             : test_instance_batch<Fq, Grumpkin>(ctx, curve, R, ck, digest, side_tag, label, n_pub, n, inst, has_E, words, n_words, chunk, multipliers, results, seconds, acc_out);
+             ? test_instance_batch<Fe, BnG1>(ctx, curve, R, ck, digest, side_tag, label, n_pub, n, inst, has_E, words, n_words, chunk, multipliers, results, seconds, acc_out, flags, leaf, stats)
+             : test_instance_batch<Fq, Grumpkin>(ctx, curve, R, ck, digest, side_tag, label, n_pub, n, inst, has_E, words, n_words, chunk, multipliers, results, seconds, acc_out, flags, leaf, stats);
   });
 }
 
 int vimz_testing_ivc_verify_compressed_batch_scalars(vimz_ivc* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0,
                                                      size_t chunk, const uint64_t* multipliers, uint32_t* results, double seconds[6]) {
+  return vimz_testing_ivc_verify_batch_compressed_scalars_ex(vk, n, blobs, lens, steps, z0, chunk, multipliers, results, seconds, 0, 0, nullptr);
+}
+int vimz_testing_ivc_verify_batch_compressed_scalars_ex(vimz_ivc* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0,
+                                                        size_t chunk, const uint64_t* multipliers, uint32_t* results, double seconds[6], uint32_t flags, size_t leaf,
+                                                        uint64_t stats[4]) {
   if (n && !multipliers) return vz_fail(vk ? vk->ctx : nullptr, VIMZ_ERR_INVALID, "vimz_testing_ivc_verify_compressed_batch_scalars: NULL multipliers");
-  return ivc_compressed_batch("vimz_testing_ivc_verify_compressed_batch_scalars", vk, n, blobs, lens, steps, z0, chunk, multipliers, results, seconds, nullptr);
+  return ivc_compressed_batch("vimz_testing_ivc_verify_compressed_batch_scalars", vk, n, blobs, lens, steps, z0, chunk, multipliers, results, seconds, nullptr, flags, leaf, stats);
 }
 int vimz_testing_cf_verify_compressed_batch_scalars(vimz_cf* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0,
                                                     size_t chunk, const uint64_t* multipliers, uint32_t* results, double seconds[6]) {
+  return vimz_testing_cf_verify_batch_compressed_scalars_ex(vk, n, blobs, lens, steps, z0, chunk, multipliers, results, seconds, 0, 0, nullptr);
+}
+int vimz_testing_cf_verify_batch_compressed_scalars_ex(vimz_cf* vk, size_t n, const uint8_t* const* blobs, const size_t* lens, const uint64_t* steps, const uint64_t* z0,
+                                                       size_t chunk, const uint64_t* multipliers, uint32_t* results, double seconds[6], uint32_t flags, size_t leaf,
+                                                       uint64_t stats[4]) {
   if (n && !multipliers) return vz_fail(vk ? vk->ctx : nullptr, VIMZ_ERR_INVALID, "vimz_testing_cf_verify_compressed_batch_scalars: NULL multipliers");
-  return cf_compressed_batch("vimz_testing_cf_verify_compressed_batch_scalars", vk, n, blobs, lens, steps, z0, chunk, multipliers, results, seconds, nullptr);
+  return cf_compressed_batch("vimz_testing_cf_verify_compressed_batch_scalars", vk, n, blobs, lens, steps, z0, chunk, multipliers, results, seconds, nullptr, flags, leaf, stats);
 }
 
 int vimz_test_spartan_eq(vimz_ctx* ctx, int field, const uint64_t* point, size_t k, uint64_t* table_out) {

@@ -13,9 +13,15 @@
 // THE BATCH EQUATION.  Every opening o gets a non-zero 128-bit multiplier ρ_o from the OS.  Per curve a chunk is accepted iff
 //   Σ_o ρ_o·[Σ_k c_{o,k}·Q_{o,k}] + (Σ_o ρ_o·g_o)·Ugen = <acc, ck>,   acc[j] = Σ_o ρ_o·afin_o·s_o[i],  j = i for an E opening, j = (i − 1) mod n for a W opening
 // (load_bases(shifted): slot 0 of a W opening is ck[n − 1], slot i is ck[i − 1]) — one MSM over the key and one over the chunk's own points per curve, both by
-// msm_run.  A failing opening survives with probability about 2^-128.  An accepted chunk adds no argument bits; a refused chunk is judged member by member by the
-// single verifier, as is every proof whose deferred pass fails anywhere inside an argument (so the bits are the single verifier's, with no second implementation
-// of them).  No bisection: one bad proof costs its chunk |chunk| single verifications.
+// msm_run.  A failing opening survives with probability about 2^-128.  An accepted chunk adds no argument bits.  Every proof whose deferred pass fails anywhere
+// inside an argument goes to the single verifier (so the bits are the single verifier's, with no second implementation of them).
+//
+// A REFUSED CHUNK IS BISECTED (batch_bisect.hpp).  What a proof costs — the parse, the transcript replay, k_mat_eval, the DefArg objects — is there already, so
+// the equation of a curve is asked again of halves of the chunk: batch_side_equation over the arguments of the members of [lo, hi), every opening under the
+// multiplier it had, i.e. k_svec_accum and the two msm_run calls again and nothing else.  A half is asked only on the curves its parent was refused on; a member
+// is accepted only inside a subset whose equations were evaluated and held; a refused subset of at most `leaf` members (default 1) goes to the single verifier.
+// At most 2·(c − 1) subsets are asked of a refused chunk of c members; one bad proof among 32 costs 5 to 10 subset equations and ONE single verification where
+// it cost 32 (profiles/batch_bisect.txt).  VIMZ_BATCH_NO_BISECT sends the refused chunk to the single verifier whole.
 //
 // Kernels: one thread an element or a row, every thread writes slots it owns, no atomics, no flag another workgroup reads, every loop bound from the host (or the
 // uploaded CSR), partials reduced by a second launch.
@@ -25,13 +31,15 @@
 #include <chrono>
 #include <functional>
 #include <thread>
+#include "batch_bisect.hpp"
 #include "spartan_batch_plan.hpp"
 
 namespace {
 
 // (spartan_batch_plan.hpp: the GPU-free pieces, with their host check)
 constexpr uint32_t BATCH_GROUP = sb::GROUP, BATCH_SPLIT_H = sb::SPLIT_H, BATCH_MAX_VARS = sb::MAX_VARS;
-constexpr size_t BATCH_DEFAULT_CHUNK = sb::DEFAULT_CHUNK;
+constexpr size_t BATCH_DEFAULT_CHUNK = sb::DEFAULT_CHUNK, BATCH_DEFAULT_LEAF = sb::DEFAULT_LEAF;
+constexpr uint32_t BATCH_NO_BISECT = 1;      // flags bit 0 (VIMZ_BATCH_NO_BISECT)
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------------------------------------------
 // per member g of a group two points t = 0, 1 of nv[t] variables each (vars[(2g + t)·BATCH_MAX_VARS + q], q = 0 the TOP bit of the index); four tables, member-
@@ -537,18 +545,24 @@ constexpr size_t BATCH_MAX_OPENINGS = 6;      // a proof brings at most three ar
 
 // What a batch entry is made of.  deferred(i, vf, &res): the single verifier's body under the DeferredVerify policy (an error code ends the call);
 // single(i, &res): the single entry itself.  given: NULL, or BATCH_MAX_OPENINGS multipliers of 2 words a proof (a test's).  seconds[6]: parse + host checks,
-// tables, matrix evaluation, s-vector accumulation, MSMs, fallback.  probe (a test's): receives the accumulators of the LAST chunk, side 0 then side 1.
+// tables, matrix evaluation, s-vector accumulation, MSMs, fallback (the subset equations of refused chunks and the single verifications).  probe (a test's):
+// receives the accumulators of the LAST chunk's full equation (never a subset's), side 0 then side 1.  flags: BATCH_NO_BISECT; leaf: 0 = the default;
+// stats[4] (optional): chunks refused, side equations evaluated after a refusal, single verifications run, members of refused chunks accepted by a subset equation.
 // An error code — a member's deferred pass or single verification returning one, no randomness, a HIP error — ends the whole call with that code; `results` is
 // then unspecified (the entries check what a caller can get wrong, a z0 element not below the modulus, before anything is written).
 struct BatchProbe { uint64_t* acc[2] = {nullptr, nullptr}; };
 inline int compressed_batch(const char* who, vimz_ctx* ctx, SpartanCache* cache, const vimz_bases* ck1, const vimz_bases* ck2, size_t n, size_t chunk, const uint64_t* given,
                             const std::function<int(size_t, DeferredVerify&, uint32_t*)>& deferred, const std::function<int(size_t, uint32_t*)>& single, uint32_t* results,
-                            double seconds[6], BatchProbe* probe) {
+                            double seconds[6], BatchProbe* probe, uint32_t flags = 0, size_t leaf = 0, uint64_t* stats = nullptr) {
   double sec[6] = {0, 0, 0, 0, 0, 0};
-  auto done = [&](int rc) { if (seconds) memcpy(seconds, sec, sizeof(sec)); return rc; };
+  uint64_t cnt[bb::ST_N] = {0, 0, 0, 0};
+  if (stats) memset(stats, 0, sizeof(cnt));
+  auto done = [&](int rc) { if (seconds) memcpy(seconds, sec, sizeof(sec)); if (stats) memcpy(stats, cnt, sizeof(cnt)); return rc; };
   auto bad = [&](const char* why) { const std::string m = std::string(who) + ": " + why; return done(vz_fail(ctx, VIMZ_ERR_INVALID, m.c_str())); };
+  if (flags & ~BATCH_NO_BISECT) return bad("unknown flag");
   if (!n) return done(VIMZ_OK);
   if (!chunk) chunk = BATCH_DEFAULT_CHUNK;
+  if (!leaf) leaf = BATCH_DEFAULT_LEAF;
   if (given)
     for (size_t q = 0; q < BATCH_MAX_OPENINGS * n; q++) if (!(given[2 * q] | given[2 * q + 1])) return bad("a multiplier is zero");
   // 1. every proof's own bits and its deferred arguments, on the process's threads
@@ -614,39 +628,82 @@ inline int compressed_batch(const char* who, vimz_ctx* ctx, SpartanCache* cache,
       };
       if ((e = mat((Fe*)nullptr, cache->side[0])) != hipSuccess) return done(vz_fail(ctx, VIMZ_ERR_HIP, who, e));
       if ((e = mat((Fq*)nullptr, cache->side[1])) != hipSuccess) return done(vz_fail(ctx, VIMZ_ERR_HIP, who, e));
-      // 2b. the equation of each curve over the openings of the proofs still in
-      std::vector<const DefArg<Fe, Fq>*> s1; std::vector<const DefArg<Fq, Fe>*> s2;
-      std::vector<uint64_t> r1, r2;
+      // 2b. the equation of each curve over the openings of the proofs still in.  A member keeps its arguments and its multipliers (its Fe arguments' openings
+      // in order, then its Fq arguments') for every subset it appears in; the copies are wiped when the chunk is settled, on every way out
+      struct Member { size_t q; std::vector<const DefArg<Fe, Fq>*> a1; std::vector<const DefArg<Fq, Fe>*> a2; std::vector<uint64_t> r1, r2; };
+      struct Members {
+        std::vector<Member> v;
+        static void wipe(Member& M) { if (!M.r1.empty()) explicit_bzero(M.r1.data(), 8 * M.r1.size()); if (!M.r2.empty()) explicit_bzero(M.r2.data(), 8 * M.r2.size()); }
+        ~Members() { for (Member& M : v) wipe(M); }
+      } in;
+      in.v.reserve(c1 - c0);
       {
         size_t o = 0;
         for (size_t q = c0; q < c1; q++) {
           DeferredVerify& V = vf[pending[q]];
-          // a proof's multipliers: its Fe arguments' openings in order, then its Fq arguments'
+          Member M; M.q = q;
           size_t k = 0;
-          auto take = [&](std::vector<uint64_t>& dst, uint32_t cnt) {
-            for (uint32_t j = 0; j < cnt; j++, k++, o++) {
+          auto take = [&](std::vector<uint64_t>& dst, uint32_t cnt_open) {
+            for (uint32_t j = 0; j < cnt_open; j++, k++, o++) {
               const uint64_t* src = given ? given + 2 * (BATCH_MAX_OPENINGS * pending[q] + k) : &X.rho[2 * o];
-              if (good[q - c0]) { dst.push_back(src[0]); dst.push_back(src[1]); }
+              dst.push_back(src[0]); dst.push_back(src[1]);
             }
           };
-          for (auto& A : V.a1) { take(r1, A.n_open); if (good[q - c0]) s1.push_back(&A); }
-          for (auto& A : V.a2) { take(r2, A.n_open); if (good[q - c0]) s2.push_back(&A); }
+          for (auto& A : V.a1) { take(M.r1, A.n_open); M.a1.push_back(&A); }
+          for (auto& A : V.a2) { take(M.r2, A.n_open); M.a2.push_back(&A); }
+          if (good[q - c0]) in.v.push_back(std::move(M)); else Members::wipe(M);
         }
       }
+      // one curve's equation over the members [lo, hi) of `in`: the chunk's, and a bisection's subsets'
+      auto side_eq = [&](size_t lo, size_t hi, int side, bool* ok, double* st, double* sec_msm, uint64_t* probe_acc) -> hipError_t {
+        std::vector<uint64_t> r;
+        hipError_t e2;
+        if (side == 0) {
+          std::vector<const DefArg<Fe, Fq>*> a;
+          for (size_t p = lo; p < hi; p++) { a.insert(a.end(), in.v[p].a1.begin(), in.v[p].a1.end()); r.insert(r.end(), in.v[p].r1.begin(), in.v[p].r1.end()); }
+          e2 = batch_side_equation<Fe, BnG1>(s, *cache, cache->side[0], D, ck1, cache->ipa_u1, a, r.data(), ok, st, sec_msm, probe_acc);
+        } else {
+          std::vector<const DefArg<Fq, Fe>*> a;
+          for (size_t p = lo; p < hi; p++) { a.insert(a.end(), in.v[p].a2.begin(), in.v[p].a2.end()); r.insert(r.end(), in.v[p].r2.begin(), in.v[p].r2.end()); }
+          e2 = batch_side_equation<Fq, Grumpkin>(s, *cache, cache->side[1], D, ck2, cache->ipa_u2, a, r.data(), ok, st, sec_msm, probe_acc);
+        }
+        if (!r.empty()) explicit_bzero(r.data(), 8 * r.size());
+        return e2;
+      };
       double st[2] = {0, 0};
-      e = batch_side_equation<Fe, BnG1>(s, *cache, cache->side[0], D, ck1, cache->ipa_u1, s1, r1.data(), &holds[0], st, &sec[4], probe ? probe->acc[0] : nullptr);
-      if (e == hipSuccess) e = batch_side_equation<Fq, Grumpkin>(s, *cache, cache->side[1], D, ck2, cache->ipa_u2, s2, r2.data(), &holds[1], st, &sec[4], probe ? probe->acc[1] : nullptr);
+      e = side_eq(0, in.v.size(), 0, &holds[0], st, &sec[4], probe ? probe->acc[0] : nullptr);
+      if (e == hipSuccess) e = side_eq(0, in.v.size(), 1, &holds[1], st, &sec[4], probe ? probe->acc[1] : nullptr);
       sec[1] += st[0]; sec[3] += st[1];
-      if (!r1.empty()) explicit_bzero(r1.data(), 8 * r1.size());
-      if (!r2.empty()) explicit_bzero(r2.data(), 8 * r2.size());
       if (e != hipSuccess) return done(vz_fail(ctx, VIMZ_ERR_HIP, who, e));
+      // 2c. a refused chunk: the same equations over halves, on the curves that refused (an accepted member keeps the word of step 1)
+      if (!(holds[0] && holds[1])) {
+        const auto tb = std::chrono::steady_clock::now();
+        const std::vector<bb::Subset> roots{{0, in.v.size(), (holds[0] ? 0u : 1u) | (holds[1] ? 0u : 2u)}};
+        bb::Outcome out;
+        if (flags & BATCH_NO_BISECT) out.singles = roots;
+        else {
+          const bool ok = bb::bisect(roots, leaf, [&](const std::vector<bb::Subset>& ask, std::vector<uint32_t>& held) {
+            for (size_t k = 0; k < ask.size(); k++)
+              for (int side = 0; side < 2; side++) {
+                if (!((ask[k].sides >> side) & 1u)) continue;
+                bool ok2 = false;
+                if ((e = side_eq(ask[k].lo, ask[k].hi, side, &ok2, nullptr, nullptr, nullptr)) != hipSuccess) return false;
+                if (ok2) held[k] |= 1u << side;
+              }
+            return true;
+          }, &out);
+          if (!ok) return done(vz_fail(ctx, VIMZ_ERR_HIP, who, e));
+        }
+        for (const bb::Subset& sgl : out.singles) for (size_t p = sgl.lo; p < sgl.hi; p++) again.push_back(pending[in.v[p].q]);
+        cnt[bb::ST_REFUSED]++; cnt[bb::ST_EQUATIONS] += out.equations; cnt[bb::ST_ACCEPTED] += out.accepted;
+        sec[5] += batch_since(tb);
+      }
     }
-    const bool accepted = holds[0] && holds[1];
-    for (size_t q = c0; q < c1; q++) if (!accepted || !good[q - c0]) again.push_back(pending[q]);      // (an accepted member keeps the word of step 1)
+    for (size_t q = c0; q < c1; q++) if (!good[q - c0]) again.push_back(pending[q]);
   }
   // 3. the single verifier for what the deferred pass or a chunk refused
   t0 = std::chrono::steady_clock::now();
-  for (size_t i : again) { const int rc = single(i, &results[i]); if (rc) return done(rc); }
+  for (size_t i : again) { const int rc = single(i, &results[i]); if (rc) return done(rc); cnt[bb::ST_SINGLES]++; }
   sec[5] += batch_since(t0);
   return done(VIMZ_OK);
 }

@@ -13,7 +13,8 @@ namespace sb {
 constexpr uint32_t GROUP = 4;          // proofs one k_mat_eval pass serves, openings one k_svec_accum pass serves
 constexpr uint32_t SPLIT_H = 10;       // a table over k variables is the product of a half-table over the low min(k, H) index bits and one over the rest
 constexpr uint32_t MAX_VARS = 24;      // variables a point may have (shapes are capped at 2^21)
-constexpr size_t DEFAULT_CHUNK = 32;   // one refused chunk costs the fallback 32 single verifications
+constexpr size_t DEFAULT_CHUNK = 32;   // (a refused chunk without bisection: 32 single verifications)
+constexpr size_t DEFAULT_LEAF = 1;     // a refused subset of one member goes to the single verifier: a subset equation costs a small fraction of one (profiles/batch_bisect.txt)
 
 // two points of nv[0], nv[1] variables -> four tables: element offsets of (point 0 low, point 0 high, point 1 low, point 1 high), and their total
 struct HalfLayout { uint32_t hl[2], off[4], elems; };

@@ -388,12 +388,14 @@ def verify_compressed_proof(verifier_key, compressed, num_steps, initial_state):
         raise _lib.VimzError(_lib.ERR_UNSAT, f"Failed to verify proof (flags {r:#x})")
 
 
-def verify_compressed_proofs(verifier_key, blobs, num_steps, initial_states, chunk=0):
+def verify_compressed_proofs(verifier_key, blobs, num_steps, initial_states, chunk=0, bisect=True, leaf=0, stats=None):
     """Many compressed proofs under one verifier key in one call (vimz_ivc_verify_compressed_batch / vimz_cf_verify_compressed_batch): the group equations of
     a chunk of proofs (0 = 32) are judged as one, on the GPU.  verifier_key: a hip.IVC for "ivc" / "merged" blobs, a hip.CycleFoldIVC for the two Nova +
     CycleFold kinds; the kinds of a family may be mixed, a blob of the other family gets the malformed bit.  Returns the flag words, one a proof — the word
-    verify_compressed_proof's entry gives for that proof alone, 0 = accepted — and does not raise on a bad member."""
-    return verifier_key.verify_compressed_batch(blobs, num_steps, initial_states, chunk)[0]
+    verify_compressed_proof's entry gives for that proof alone, 0 = accepted — and does not raise on a bad member.  A refused chunk is bisected: its equations
+    are asked again of halves, down to refused subsets of `leaf` proofs (0 = 1), which the single verifier judges; bisect=False sends the chunk there whole.
+    stats: a dict that receives hip.BATCH_STATS (chunks refused, subset equations, single verifications, members a subset equation accepted)."""
+    return verifier_key.verify_compressed_batch(blobs, num_steps, initial_states, chunk, bisect=bisect, leaf=leaf, stats=stats)[0]
 
 
 # ---- a proof's final state against its images (the Sonobe path's verify_final_state_arkworks, vimz/src/sonobe_backend/folding.rs:77-132) ----

@@ -672,10 +672,11 @@ class IVC:
         self.ctx._chk(lib.vimz_ivc_verify_compressed(self.h, _ptr(b), b.size, int(num_steps), _ptr(z), C.byref(r)))
         return r.value
 
-    def verify_compressed_batch(self, blobs, num_steps, initial_states, chunk=0):
+    def verify_compressed_batch(self, blobs, num_steps, initial_states, chunk=0, bisect=True, leaf=0, stats=None):
         """vimz_ivc_verify_compressed_batch: many compressed proofs ("ivc" and "merged" kinds, mixed as they come) under this verifier key in one call.
-        Returns (words, seconds): words[i] is what verify_compressed / MergedProof.verify_compressed gives for proof i alone."""
-        return _compressed_batch(self, "vimz_ivc_verify_compressed_batch", blobs, num_steps, initial_states, chunk)
+        Returns (words, seconds): words[i] is what verify_compressed / MergedProof.verify_compressed gives for proof i alone.
+        bisect, leaf, stats: as verify_decider_batch takes them (a refused chunk is bisected; leaf 0 = 1)."""
+        return _compressed_batch(self, "vimz_ivc_verify_compressed_batch", blobs, num_steps, initial_states, chunk, bisect=bisect, leaf=leaf, stats=stats)
 
     def export(self, side, what):
         """(n, 4) uint64 canonical elements."""
@@ -773,10 +774,10 @@ class CycleFoldIVC:
         self.ctx._chk(lib.vimz_cf_verify_compressed(self.h, _ptr(b), b.size, int(num_steps), _ptr(_zlimbs(z0, self.circuit.len_z)), C.byref(r)))
         return r.value
 
-    def verify_compressed_batch(self, blobs, num_steps, initial_states, chunk=0):
+    def verify_compressed_batch(self, blobs, num_steps, initial_states, chunk=0, bisect=True, leaf=0, stats=None):
         """vimz_cf_verify_compressed_batch: many compressed Nova + CycleFold proofs ("cyclefold" and "cyclefold-merged", mixed) under this verifier key in
         one call.  Returns (words, seconds): words[i] is what the single verifier gives for proof i alone."""
-        return _compressed_batch(self, "vimz_cf_verify_compressed_batch", blobs, num_steps, initial_states, chunk)
+        return _compressed_batch(self, "vimz_cf_verify_compressed_batch", blobs, num_steps, initial_states, chunk, bisect=bisect, leaf=leaf, stats=stats)
 
     def poke(self, which, index, value):
         """Test hook (vimz_cf_poke, include/vimz_hip_testing.h): exists only when the process runs on libvimz_hip_testing.so
@@ -1498,10 +1499,10 @@ class Decider:
         self.ctx._chk(self.ctx.lib.vimz_decider_verify(self.h, int(steps), _ptr(z0a), _ptr(zia), _ptr(wa), C.byref(res)))
         return int(res.value)
 
-    def verify_batch(self, items, chunk=0):
+    def verify_batch(self, items, chunk=0, bisect=True, leaf=0, stats=None):
         """Decider::verify for many (steps, z0, z_i, words) at once, over this decider's key words and context (verify_decider_batch): the list of result bits,
-        each what `verify` gives for that proof alone."""
-        return verify_decider_batch(self.ctx, self.key_words(), items, chunk=chunk)
+        each what `verify` gives for that proof alone.  bisect, leaf, stats: as verify_decider_batch takes them."""
+        return verify_decider_batch(self.ctx, self.key_words(), items, chunk=chunk, bisect=bisect, leaf=leaf, stats=stats)
 
 
 def parse_verifying_key(w):
@@ -1568,11 +1569,21 @@ def decider_verify_key(key_words, steps, z0, z_i, words):
     return int(res.value)
 
 
-def verify_decider_batch(ctx, key_words, items, chunk=0, seconds=None, multipliers=None):
+BATCH_NO_BISECT = 1          # VIMZ_BATCH_NO_BISECT
+BATCH_STATS = ("chunks_refused", "subset_equations", "single_verifications", "accepted_by_subset")
+
+
+def _batch_tail(bisect, leaf):
+    """(flags, leaf, stats[4]) of the batch verifiers' _ex entries"""
+    return (0 if bisect else BATCH_NO_BISECT), int(leaf), (C.c_uint64 * 4)()
+
+
+def verify_decider_batch(ctx, key_words, items, chunk=0, seconds=None, multipliers=None, bisect=True, leaf=0, stats=None):
     """vimz_decider_verify_batch: many proofs under one key.  items: a sequence of (steps, z0, z_i, words) as Decider.verify takes them (calldata.decode's
     "steps", "z0", "z_i", "proof").  ctx: a Context — the per-proof part runs on the GPU — or None: the same batch on the host's threads, no GPU.  Returns the list
     of result bits, each what decider_verify_key gives for that proof alone.  seconds: a dict that receives the call's split.  multipliers (tests only, testing
-    library): 3 ints a proof in place of the OS's randomness."""
+    library): 3 ints a proof in place of the OS's randomness.  A refused chunk is bisected down to refused subsets of at most `leaf` proofs (0: the library's
+    default), which the single verifier judges; bisect=False sends it there whole.  The words are the same either way.  stats: a dict that receives BATCH_STATS."""
     lib = L.lib() if ctx is None else ctx.lib
     vp = C.c_void_p
     kw = np.ascontiguousarray(key_words, dtype=np.uint64)
@@ -1591,14 +1602,16 @@ def verify_decider_batch(ctx, key_words, items, chunk=0, seconds=None, multiplie
     sec = (C.c_double * 6)()
     head = [None if ctx is None else ctx.h, _ptr(kw), kw.size, len_z, n, _ptr(steps), _ptr(z0a), _ptr(zia), _ptr(wa), int(chunk)]
     types = [vp, vp, C.c_size_t, C.c_uint32, C.c_size_t, vp, vp, vp, vp, C.c_size_t]
+    flags, leaf, st = _batch_tail(bisect, leaf)
+    tail = [C.c_uint32, C.c_size_t, C.POINTER(C.c_uint64)]
     if multipliers is None:
-        lib.vimz_decider_verify_batch.argtypes = types + [vp, C.POINTER(C.c_double)]
-        rc = lib.vimz_decider_verify_batch(*head, _ptr(res), sec)
+        lib.vimz_decider_verify_batch_ex.argtypes = types + [vp, C.POINTER(C.c_double)] + tail
+        rc = lib.vimz_decider_verify_batch_ex(*head, _ptr(res), sec, flags, leaf, st)
     else:
-        fn = L.testing_lib().vimz_testing_decider_verify_batch_scalars
-        fn.argtypes = types + [vp, vp, C.POINTER(C.c_double)]
+        fn = L.testing_lib().vimz_testing_decider_verify_batch_scalars_ex
+        fn.argtypes = types + [vp, vp, C.POINTER(C.c_double)] + tail
         ma = np.frombuffer(b"".join(int(x).to_bytes(16, "little") for x in multipliers), dtype="<u8").astype(np.uint64)
-        rc = fn(*head, _ptr(ma), _ptr(res), sec)
+        rc = fn(*head, _ptr(ma), _ptr(res), sec, flags, leaf, st)
     if rc:
         if ctx is not None:
             ctx._chk(rc)
@@ -1606,6 +1619,8 @@ def verify_decider_batch(ctx, key_words, items, chunk=0, seconds=None, multiplie
         raise L.VimzError(rc, (lib.vimz_last_error(None) or b"vimz_decider_verify_batch").decode())
     if seconds is not None:
         seconds.update(zip(("parse_and_host", "per_proof_stage", "miller_loops", "chunk_products", "fallback", "total"), (float(x) for x in sec)))
+    if stats is not None:
+        stats.update(zip(BATCH_STATS, (int(x) for x in st)))
     return [int(x) for x in res[:n]]
 
 
@@ -1844,8 +1859,9 @@ def _zlimbs(z0, len_z):
     return z
 
 
-def _compressed_batch(vk, entry, blobs, num_steps, initial_states, chunk, multipliers=None):
-    """The shared body of IVC.verify_compressed_batch and CycleFoldIVC.verify_compressed_batch: (flag words, seconds split)."""
+def _compressed_batch(vk, entry, blobs, num_steps, initial_states, chunk, multipliers=None, bisect=True, leaf=0, stats=None):
+    """The shared body of IVC.verify_compressed_batch and CycleFoldIVC.verify_compressed_batch: (flag words, seconds split).  entry: the entry without _ex (its twin
+    vimz_*_verify_batch_compressed*_ex is what runs).  bisect, leaf, stats: as verify_decider_batch takes them; "subset_equations" counts one a curve asked."""
     lib = vk.ctx.lib
     n = len(blobs)
     if len(num_steps) != n or len(initial_states) != n:
@@ -1862,15 +1878,19 @@ def _compressed_batch(vk, entry, blobs, num_steps, initial_states, chunk, multip
     res = np.zeros(max(n, 1), dtype=np.uint32)
     sec = (C.c_double * 6)()
     vp, sz = C.c_void_p, C.c_size_t
-    fn = getattr(lib, entry)
+    fn = getattr(lib, entry.replace("verify_compressed_batch", "verify_batch_compressed") + "_ex")
+    flags, leaf, st = _batch_tail(bisect, leaf)
+    tail = [C.c_uint32, sz, C.POINTER(C.c_uint64)]
     if multipliers is None:
-        fn.argtypes = [vp, sz, vp, vp, vp, vp, sz, vp, C.POINTER(C.c_double)]
-        rc = fn(vk.h, n, ptrs, lens, _ptr(steps), _ptr(z), int(chunk), _ptr(res), sec)
+        fn.argtypes = [vp, sz, vp, vp, vp, vp, sz, vp, C.POINTER(C.c_double)] + tail
+        rc = fn(vk.h, n, ptrs, lens, _ptr(steps), _ptr(z), int(chunk), _ptr(res), sec, flags, leaf, st)
     else:
         m = np.ascontiguousarray(multipliers, dtype=np.uint64).reshape(-1)
-        fn.argtypes = [vp, sz, vp, vp, vp, vp, sz, vp, vp, C.POINTER(C.c_double)]
-        rc = fn(vk.h, n, ptrs, lens, _ptr(steps), _ptr(z), int(chunk), _ptr(m), _ptr(res), sec)
+        fn.argtypes = [vp, sz, vp, vp, vp, vp, sz, vp, vp, C.POINTER(C.c_double)] + tail
+        rc = fn(vk.h, n, ptrs, lens, _ptr(steps), _ptr(z), int(chunk), _ptr(m), _ptr(res), sec, flags, leaf, st)
     vk.ctx._chk(rc)
+    if stats is not None:
+        stats.update(zip(BATCH_STATS, (int(x) for x in st)))
     names = ("parse_and_host_checks_s", "tables_s", "matrix_evaluation_s", "svec_accumulation_s", "msm_s", "fallback_s")
     return [int(x) for x in res[:n]], dict(zip(names, list(sec)))
 
