@@ -63,6 +63,28 @@ int vimz_test_spmv_cross16(vimz_ctx* ctx, const vimz_r1cs* S, size_t row0, size_
  * where az2_i is one, zero where it is zero, T_i + az1_i where it is anything else; T_i from nb on (instance 2 is the fresh one). */
 int vimz_test_cross_term_masked(vimz_ctx* ctx, size_t n, const vimz_vec* az1, const vimz_vec* bz1, const vimz_vec* cz1, const uint64_t u1[4], const vimz_vec* az2,
                                 const vimz_vec* bz2, const vimz_vec* cz2, const uint64_t u2[4], int form, vimz_vec* T, vimz_vec* Tm, size_t nb);
+/* The element-wise kernels of a fold step (vimz_amd/csrc/r1cs_ops.hpp) on a caller's vectors, each through the product's kernel template with the product's block size
+ * (tests/test_gpu_fold_kernels.py; the reference and the cases: tests/_fold_ref.py).  All four fields; scalars: 4 words, form = VIMZ_FORM_*.  blocks = 0: the product's
+ * grid — stream_grid(n) for k_fold_cross and k_fresh_cross_neg, 2048 for k_fold5 —, blocks in 1..2048: that grid, so that a few hundred elements reach the grid stride.
+ * Every length, field and alias is checked before anything is launched (VIMZ_ERR_INVALID with a message).
+ * _fold_cross: k_fold_cross over n elements — (AZ, BZ, CZ) += r·(az, bz, cz); with fold_E: E += r·(Tin − hasB·r_prev·negB), E left alone where that vector is zero; with
+ *   out: out = AZ'∘bzn + BZ'∘azn − u1_new·czn − u2·CZ' of the folded products and, with outm, its boolean-row form over the first nb elements (as
+ *   vimz_test_cross_term_masked's Tm).  Tin may be NULL without fold_E, negB unless fold_E and hasB; out NULL: no cross term (azn, bzn, czn, outm then unused).  out
+ *   may be the very vector passed as Tin — what the lookahead does —; every other vector written must be one of its own, outm differ from out.
+ * _fold5: k_fold5 over five groups: x1[v][off1[v] .. + n[v]) += r·x2[v][off2[v] .. + n[v]), offsets in elements; x1[v] NULL: the group is skipped (the error vector at
+ *   step 0).  A range written must overlap no other range of the call.
+ * _fresh_cross_neg: k_fresh_cross_neg over n elements of two fresh product triples: out = cz0 + cz1 − az0∘bz1 − az1∘bz0.
+ * _count: one of the counting kernels that guard imported and merged proofs, over the first n elements, on a counter the hook zeroes: what = 0, k_count_unreduced —
+ *   the elements of a whose words as they lie are not below the modulus (upload them with VIMZ_FORM_MONTGOMERY: copied as they are) —; what = 1, k_count_diff — the
+ *   elements at which a and b differ in any word. */
+int vimz_test_fold_cross(vimz_ctx* ctx, size_t n, vimz_vec* AZ, vimz_vec* BZ, vimz_vec* CZ, vimz_vec* E, const vimz_vec* Tin, int fold_E, const uint64_t r[4], int hasB,
+                         const uint64_t r_prev[4], const vimz_vec* negB, const uint64_t u1_new[4], const vimz_vec* az, const vimz_vec* bz, const vimz_vec* cz, vimz_vec* out,
+                         const vimz_vec* azn, const vimz_vec* bzn, const vimz_vec* czn, const uint64_t u2[4], int form, vimz_vec* outm, size_t nb, unsigned blocks);
+int vimz_test_fold5(vimz_ctx* ctx, vimz_vec* const x1[5], const size_t off1[5], const vimz_vec* const x2[5], const size_t off2[5], const size_t n[5], const uint64_t r[4], int form,
+                    unsigned blocks);
+int vimz_test_fresh_cross_neg(vimz_ctx* ctx, size_t n, const vimz_vec* az0, const vimz_vec* bz0, const vimz_vec* cz0, const vimz_vec* az1, const vimz_vec* bz1, const vimz_vec* cz1,
+                              vimz_vec* out, unsigned blocks);
+int vimz_test_count(vimz_ctx* ctx, int what, size_t n, const vimz_vec* a, const vimz_vec* b, uint64_t* count);
 /* msm_launch_rows (vimz_amd/csrc/msm.hpp) on a caller's rows: G (<= 16) vectors of n scalars each, row r at scalars + 4·r·row_stride words of 64 bits (host;
  * form = VIMZ_FORM_*), committed over the first n points of a BN254 G1 key as ONE chain of launches with the unit scalars split off — with the key's shared-bucket
  * window tables (use_tables != 0; vimz_bases_precompute first) or without — `calls` times over on ONE fresh workspace.  out_xy: calls·G affine points

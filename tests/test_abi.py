@@ -39,7 +39,8 @@ def test_test_hooks_are_not_in_the_product_library():
     assert {"vimz_cf_poke", "vimz_cf_selfcheck", "vimz_worker_selftest", "vimz_test_forge_public_slot", "vimz_strict_bits_selfcheck",
             "vimz_test_fp29_probe", "vimz_test_spmv_cross16", "vimz_test_cross_term_masked", "vimz_test_g16_domain", "vimz_test_g16_fixed_mul",
             "vimz_test_g16_g2_msm", "vimz_test_msm_scan", "vimz_test_msm_combine", "vimz_test_msm_reduce", "vimz_test_msm_tree", "vimz_test_quad_level",
-            "vimz_test_msm_sort", "vimz_test_msm_accum", "vimz_test_msm_small", "vimz_test_msm_fixed", "vimz_test_msm_ones", "vimz_test_bases_tables"} <= set(hooks)
+            "vimz_test_msm_sort", "vimz_test_msm_accum", "vimz_test_msm_small", "vimz_test_msm_fixed", "vimz_test_msm_ones", "vimz_test_bases_tables",
+            "vimz_test_fold_cross", "vimz_test_fold5", "vimz_test_fresh_cross_neg", "vimz_test_count"} <= set(hooks)
     P = ctypes.CDLL(_lib.PRODUCT_SO_PATH)
     leaked = [s for s in hooks if hasattr(P, s)]
     assert not leaked, f"test hooks exported by the product library: {leaked}"

@@ -363,5 +363,133 @@ int vimz_test_cross_term_masked(vimz_ctx* ctx, size_t n, const vimz_vec* az1, co
   return VIMZ_OK;
 }
 
+// ---- the fold step kernels (k_fold_cross, k_fold5, k_fresh_cross_neg) and the two counting kernels, each as the product launches it -------------------
+int vimz_test_fold_cross(vimz_ctx* ctx, size_t n, vimz_vec* AZ, vimz_vec* BZ, vimz_vec* CZ, vimz_vec* E, const vimz_vec* Tin, int fold_E, const uint64_t r[4], int hasB,
+                         const uint64_t r_prev[4], const vimz_vec* negB, const uint64_t u1_new[4], const vimz_vec* az, const vimz_vec* bz, const vimz_vec* cz, vimz_vec* out,
+                         const vimz_vec* azn, const vimz_vec* bzn, const vimz_vec* czn, const uint64_t u2[4], int form, vimz_vec* outm, size_t nb, unsigned blocks) {
+  if (!ctx || !AZ || !BZ || !CZ || !E || !r || !r_prev || !u1_new || !u2 || !az || !bz || !cz) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_fold_cross: bad argument");
+  if (fold_E && !Tin) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_fold_cross: fold_E needs Tin");
+  if (fold_E && hasB && !negB) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_fold_cross: hasB needs negB");
+  if (out && (!azn || !bzn || !czn)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_fold_cross: out needs azn, bzn and czn");
+  if (outm && !out) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_fold_cross: outm needs out");
+  const vimz_vec* wr[6] = {AZ, BZ, CZ, E, out, outm};
+  const vimz_vec* rd[8] = {az, bz, cz, azn, bzn, czn, negB, Tin};
+  for (const vimz_vec* v : wr) if (v && (v->field != AZ->field || v->n < n)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_fold_cross: field or length of a vector");
+  for (const vimz_vec* v : rd) if (v && (v->field != AZ->field || v->n < n)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_fold_cross: field or length of a vector");
+  if (nb > n || n >= (1ull << 32) || blocks > 2048) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_fold_cross: nb beyond n, or blocks above 2048");
+  // every vector written is one of its own; the one alias the product makes is out == Tin (element-wise, read first)
+  for (int i = 0; i < 6; i++) {
+    for (int j = i + 1; j < 6; j++) if (wr[i] && wr[i] == wr[j]) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_fold_cross: two outputs are the same vector");
+    for (int j = 0; j < 8; j++)
+      if (wr[i] && wr[i] == rd[j] && !(wr[i] == out && rd[j] == Tin && j == 7)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_fold_cross: an output is also an input (only out may be Tin)");
+  }
+  if (!n) return VIMZ_OK;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  R_TRY(hipSetDevice(ctx->device));
+  int rc = field_dispatch(AZ->field, [&](auto f) {
+    typedef decltype(f) F;
+    F fr, fp, fu1, fu2; int q;
+    if ((q = scalar_arg(ctx, r, form, &fr, "vimz_test_fold_cross: r not below the modulus")) || (q = scalar_arg(ctx, r_prev, form, &fp, "vimz_test_fold_cross: r_prev not below the modulus")) ||
+        (q = scalar_arg(ctx, u1_new, form, &fu1, "vimz_test_fold_cross: u1_new not below the modulus")) || (q = scalar_arg(ctx, u2, form, &fu2, "vimz_test_fold_cross: u2 not below the modulus")))
+      return q;
+    auto ro = [](const vimz_vec* v) { return v ? (const uint32_t*)v->d : (const uint32_t*)nullptr; };
+    hipLaunchKernelGGL(k_fold_cross<F>, dim3(blocks ? blocks : stream_grid(n)), dim3(256), 0, ctx->stream, n, AZ->d, BZ->d, CZ->d, E->d, ro(Tin), fold_E ? 1 : 0, fr, hasB ? 1 : 0, fp,
+                       ro(negB), fu1, ro(az), ro(bz), ro(cz), out ? out->d : (uint32_t*)nullptr, ro(azn), ro(bzn), ro(czn), fu2, outm ? outm->d : (uint32_t*)nullptr, (uint32_t)nb);
+    return VIMZ_OK;
+  });
+  if (rc) return rc;
+  R_TRY(hipGetLastError());
+  R_TRY(hipStreamSynchronize(ctx->stream));
+  return VIMZ_OK;
+}
+
+int vimz_test_fold5(vimz_ctx* ctx, vimz_vec* const x1[5], const size_t off1[5], const vimz_vec* const x2[5], const size_t off2[5], const size_t n[5], const uint64_t r[4], int form,
+                    unsigned blocks) {
+  if (!ctx || !x1 || !off1 || !x2 || !off2 || !n || !r || blocks > 2048) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_fold5: bad argument");
+  int field = -1;
+  for (int v = 0; v < 5; v++) {
+    if (!x2[v]) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_fold5: x2 missing");
+    if (field < 0) field = x2[v]->field;
+    if (x2[v]->field != field || (x1[v] && x1[v]->field != field)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_fold5: fields differ");
+    if (off2[v] > x2[v]->n || n[v] > x2[v]->n - off2[v] || (x1[v] && (off1[v] > x1[v]->n || n[v] > x1[v]->n - off1[v])))
+      return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_fold5: a range outside its vector");
+  }
+  // a range written overlaps no other range, written or read
+  auto overlap = [](const vimz_vec* a, size_t ao, size_t an, const vimz_vec* b, size_t bo, size_t bn) { return a == b && an && bn && ao < bo + bn && bo < ao + an; };
+  for (int v = 0; v < 5; v++) {
+    if (!x1[v]) continue;
+    for (int w = 0; w < 5; w++)
+      if ((w > v && x1[w] && overlap(x1[v], off1[v], n[v], x1[w], off1[w], n[w])) || overlap(x1[v], off1[v], n[v], x2[w], off2[w], n[w]))
+        return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_fold5: a range written overlaps another range");
+  }
+  std::lock_guard<std::mutex> g(ctx->mu);
+  R_TRY(hipSetDevice(ctx->device));
+  int rc = field_dispatch(field, [&](auto f) {
+    typedef decltype(f) F;
+    F fr; int q;
+    if ((q = scalar_arg(ctx, r, form, &fr, "vimz_test_fold5: r not below the modulus"))) return q;
+    Fold5 a;
+    for (int v = 0; v < 5; v++) { a.x1[v] = x1[v] ? x1[v]->d + 8 * off1[v] : nullptr; a.x2[v] = x2[v]->d + 8 * off2[v]; a.n[v] = n[v]; }
+    hipLaunchKernelGGL(k_fold5<F>, dim3(blocks ? blocks : 2048), dim3(256), 0, ctx->stream, a, fr);
+    return VIMZ_OK;
+  });
+  if (rc) return rc;
+  R_TRY(hipGetLastError());
+  R_TRY(hipStreamSynchronize(ctx->stream));
+  return VIMZ_OK;
+}
+
+int vimz_test_fresh_cross_neg(vimz_ctx* ctx, size_t n, const vimz_vec* az0, const vimz_vec* bz0, const vimz_vec* cz0, const vimz_vec* az1, const vimz_vec* bz1, const vimz_vec* cz1,
+                              vimz_vec* out, unsigned blocks) {
+  if (!ctx || !az0 || !bz0 || !cz0 || !az1 || !bz1 || !cz1 || !out || blocks > 2048) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_fresh_cross_neg: bad argument");
+  const vimz_vec* vs[6] = {az0, bz0, cz0, az1, bz1, cz1};
+  for (const vimz_vec* v : vs) {
+    if (v->field != out->field || v->n < n) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_fresh_cross_neg: field or length of a vector");
+    if (v == out) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_fresh_cross_neg: out is also an input");
+  }
+  if (out->n < n) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_fresh_cross_neg: field or length of a vector");
+  if (!n) return VIMZ_OK;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  R_TRY(hipSetDevice(ctx->device));
+  field_dispatch(out->field, [&](auto f) {
+    typedef decltype(f) F;
+    hipLaunchKernelGGL(k_fresh_cross_neg<F>, dim3(blocks ? blocks : stream_grid(n)), dim3(256), 0, ctx->stream, n, (const uint32_t*)az0->d, (const uint32_t*)bz0->d, (const uint32_t*)cz0->d,
+                       (const uint32_t*)az1->d, (const uint32_t*)bz1->d, (const uint32_t*)cz1->d, out->d);
+    return VIMZ_OK;
+  });
+  R_TRY(hipGetLastError());
+  R_TRY(hipStreamSynchronize(ctx->stream));
+  return VIMZ_OK;
+}
+
+int vimz_test_count(vimz_ctx* ctx, int what, size_t n, const vimz_vec* a, const vimz_vec* b, uint64_t* count) {
+  if (!ctx || !a || !count || (what != 0 && what != 1) || (what == 1 && !b)) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_count: bad argument");
+  if (a->n < n || (what == 1 && (b->n < n || b->field != a->field))) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_test_count: field or length of a vector");
+  *count = 0;
+  if (!n) return VIMZ_OK;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  R_TRY(hipSetDevice(ctx->device));
+  uint32_t* bad_d = nullptr;
+  R_TRY(hipMalloc((void**)&bad_d, 4));
+  hipError_t e = hipMemsetAsync(bad_d, 0, 4, ctx->stream);
+  if (e == hipSuccess) {
+    if (what == 1) hipLaunchKernelGGL(k_count_diff, dim3(stream_grid(n)), dim3(256), 0, ctx->stream, n, (const uint32_t*)a->d, (const uint32_t*)b->d, bad_d);
+    else field_dispatch(a->field, [&](auto f) {
+      typedef decltype(f) F;
+      hipLaunchKernelGGL(k_count_unreduced<F>, dim3(stream_grid(n)), dim3(256), 0, ctx->stream, n, (const uint32_t*)a->d, bad_d);
+      return VIMZ_OK;
+    });
+    e = hipGetLastError();
+  }
+  uint32_t bad = 0;
+  if (e == hipSuccess) e = hipMemcpyAsync(&bad, bad_d, 4, hipMemcpyDeviceToHost, ctx->stream);
+  const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+  hipFree(bad_d);
+  if (e != hipSuccess) return vz_fail(ctx, VIMZ_ERR_HIP, "vimz_test_count", e);
+  if (e2 != hipSuccess) return vz_fail(ctx, VIMZ_ERR_HIP, "vimz_test_count: synchronize", e2);
+  *count = bad;
+  return VIMZ_OK;
+}
+
 }  // extern "C"
 #endif  // VIMZ_TESTING
