@@ -408,6 +408,23 @@ int vimz_ivc_verify_compressed(vimz_ivc* v, const uint8_t* blob, size_t len, uin
 int vimz_kzg_open(vimz_ctx* ctx, const vimz_bases* srs, size_t base_offset, const vimz_vec* v, size_t offset, size_t n, const uint64_t z[4], int form,
                   uint64_t eval_out[4], uint64_t proof_xy[8]);
 
+/* Multilinear KZG opening of a committed, device-resident vector over the same SRS: v of n <= N = 2^logn elements of BN254 Fr, read as
+ * zero-padded to N, is the multilinear polynomial with v[i] at the corner whose k-th coordinate is the k-th LOWEST bit of i; comm_out = Σ v[i]·srs[i] (what
+ * vimz_msm_vec gives), eval_out = its value at point (logn elements), proof = vimz_mlkzg_proof_words(logn) = 20·logn + 16 words.  Everything canonical.
+ * seconds (optional) = {folds and their commitments, evaluations, batching and divisions, the three quotient commitments}.  Refused with a message: logn = 0 or
+ * above 26, n = 0 or above 2^logn, an SRS shorter than 2^logn, a vector not over BN254 Fr or a key not on BN254 G1, a point element not below r, a short cap_words. */
+size_t vimz_mlkzg_proof_words(uint32_t logn);      /* 0 for a logn out of range */
+int vimz_mlkzg_open(vimz_ctx* ctx, const vimz_bases* srs, const vimz_vec* v, size_t offset, size_t n, uint32_t logn, const uint64_t* point, uint64_t comm_out[8],
+                    uint64_t eval_out[4], uint64_t* proof, size_t cap_words, double seconds[4]);
+/* The verifier: host only, no context, no GPU.  vk_g2 = [tau]G2 (x.c0, x.c1, y.c0, y.c1).  *result = 0 accepted, else ONE of VIMZ_MLKZG_* — each stage runs
+ * only if the earlier ones found nothing.  A NULL pointer or logn = 0 is VIMZ_ERR_INVALID; everything else is a verdict. */
+#define VIMZ_MLKZG_MALFORMED 1u      /* wrong word count, logn out of range, an element not below r, a coordinate not below q */
+#define VIMZ_MLKZG_OFF_CURVE 2u      /* comm, a C_k or a W off the curve (vk_g2 off the twist or outside the subgroup) */
+#define VIMZ_MLKZG_FOLD 4u           /* a fold equation between the claimed evaluations fails, or the challenge r is zero */
+#define VIMZ_MLKZG_PAIRING 8u        /* the batched pairing equation fails */
+int vimz_mlkzg_verify(const uint64_t vk_g2[16], const uint64_t comm[8], uint32_t logn, const uint64_t* point, const uint64_t eval[4], const uint64_t* proof,
+                      size_t n_words, uint32_t* result);
+
 /* ---- Nova + CycleFold IVC: the `prove_step` loop of the reference's Sonobe backend (vimz/src/sonobe_backend/folding.rs:52-66; scheme
  *      `Nova<G1, G2, C, KZG<Bn254>, Pedersen<G2>, false>`, folding.rs:22) — SURVEY.md §8 row N1.  The main circuit F' (step circuit + our
  *      statement of CycleFold's augmented circuit, vimz_amd/csrc/aug/cyclefold.hpp) is committed on BN254 G1 — ck_main may be a KZG SRS's
@@ -440,6 +457,10 @@ int64_t vimz_cf_export(vimz_cf* v, int side, int what, void* buf, size_t cap);
 /* KZG openings of the running main instance's commitments at z (vimz_kzg_open over ck_main as the SRS): which = 0 comm_W (coefficients = the witness
  * wires [1, wires - 2) of the running vector), 1 comm_E.  Canonical in and out. */
 int vimz_cf_kzg_open(vimz_cf* v, int which, const uint64_t z[4], uint64_t eval_out[4], uint64_t proof_xy[8]);
+/* ... and their multilinear openings at `point` (vimz_mlkzg_open over the same two vectors): logn must be the least with 2^logn >= the vector's length
+ * (wires - 3 for which = 0, the constraints for 1); comm_out is the instance's comm_W / comm_E. */
+int vimz_cf_mlkzg_open(vimz_cf* v, int which, const uint64_t* point, uint32_t logn, uint64_t comm_out[8], uint64_t eval_out[4], uint64_t* proof, size_t cap_words,
+                       double seconds[4]);
 /* The proof as an object of its own (Sonobe's `ivc_proof()` / `from_ivc_proof`; checkpoint / resume): everything vimz_cf_verify reads and the
  * next vimz_cf_fold needs.  Import into a vimz_cf created for the same step circuit and keys, then verify or keep folding. */
 size_t vimz_cf_proof_size(const vimz_cf* v);
@@ -483,6 +504,9 @@ int64_t vimz_cf_merged_export(vimz_cf_merged* m, int side, int what, void* buf, 
 /* KZG openings (vimz_kzg_open over ck_main as the SRS) of the FOLDED main instance: which = 0 comm_W, 1 comm_E.  For a merged proof of one segment the
  * folded instance is U_{i+1} = NIFS(U_i, u_i), the one Sonobe's decider opens (decider.rs:13-21).  Canonical in and out. */
 int vimz_cf_merged_kzg_open(vimz_cf_merged* m, int which, const uint64_t z[4], uint64_t eval_out[4], uint64_t proof_xy[8]);
+/* ... and their multilinear openings, as vimz_cf_mlkzg_open */
+int vimz_cf_merged_mlkzg_open(vimz_cf_merged* m, int which, const uint64_t* point, uint32_t logn, uint64_t comm_out[8], uint64_t eval_out[4], uint64_t* proof,
+                              size_t cap_words, double seconds[4]);
 /* IVC state chain only (as vimz_ivc_state_chain): the state at which a row segment proven by another vimz_cf starts */
 int vimz_cf_state_chain(vimz_cf* v, const uint64_t* z_start, const uint64_t* step_inputs, size_t nsteps, uint64_t* zs_out);
 /* ... in its two parts, as vimz_ivc_row_digests / vimz_ivc_chain_from_digests */

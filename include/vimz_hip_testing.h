@@ -356,6 +356,25 @@ int vimz_testing_cf_verify_batch_compressed_scalars_ex(vimz_cf* vk, size_t n, co
  * 0 when values[i] is no square (the root is then unspecified).  Reaches the branch for c1 = 0, which no curve point one can craft cheaply takes.  1 <= n <= 2^20. */
 int vimz_test_fq2_sqrt(vimz_ctx* ctx, const uint64_t* values, size_t n, uint64_t* roots_out, uint32_t* is_square_out);
 
+/* The multilinear KZG opening's kernels (vimz_amd/csrc/mlkzg.hip) on a caller's vectors (tests/test_gpu_mlkzg_kernels.py).  Elements are canonical, 4 words each,
+ * below r (else VIMZ_ERR_INVALID); sizes up to 2^20.  The levels of a polynomial of n0 coefficients lie side by side, level k with n0 >> k elements.
+ *   shape    out = {threads of a block, coefficients of one thread}: the sizes at which the evaluation and the division change path
+ *   fold     k_mle_fold logn times over vec (2^logn elements) at point: levels_out receives all logn + 1 levels, 2^(logn+1) - 1 elements
+ *   eval3    k_poly_eval3 + k_eval3_sum over nlevels levels (n0 >> (nlevels - 1) >= 1): evals_out[u·nlevels + k] = P_k at r, -r, r² for u = 0, 1, 2
+ *   batch    k_batch_levels: out[j] = Σ_{k: j < n0 >> k} q^k·P_k[j], n0 elements
+ *   divide   the three launches of the division of n coefficients by (X - u_j), j < 3: quot_out[j·(n-1) ..] the n - 1 quotient coefficients, rem_out[j] the
+ *            remainder, and what the first and the second launch leave, ceil(n / coefficients of a thread) elements a row (optional): carry_out each chunk's
+ *            carry-out with a zero carry-in, carry_in_out the carry into each chunk
+ *   chains   host only: label, then (tag, n bytes of data) absorbed and a challenge drawn, twice over, by proof_io.hpp's Transcript (out[0..2)) and by
+ *            mlkzg_verify.hpp's restatement of it (out[2..4)): the 128-bit challenges of the last round, or of the first round in which they differ */
+int vimz_test_mlkzg_chains(const char* label, const char* tag, const uint8_t* data, size_t n, uint64_t out[4]);
+int vimz_test_mlkzg_shape(uint32_t out[2]);
+int vimz_test_mlkzg_fold(vimz_ctx* ctx, const uint64_t* vec, uint32_t logn, const uint64_t* point, uint64_t* levels_out);
+int vimz_test_mlkzg_eval3(vimz_ctx* ctx, const uint64_t* levels, size_t n0, uint32_t nlevels, const uint64_t r[4], uint64_t* evals_out);
+int vimz_test_mlkzg_batch(vimz_ctx* ctx, const uint64_t* levels, size_t n0, uint32_t nlevels, const uint64_t q[4], uint64_t* out);
+int vimz_test_mlkzg_divide(vimz_ctx* ctx, const uint64_t* coeffs, size_t n, const uint64_t u[12], uint64_t* quot_out, uint64_t rem_out[12], uint64_t* carry_out,
+                           uint64_t* carry_in_out);
+
 #ifdef __cplusplus
 }
 #endif

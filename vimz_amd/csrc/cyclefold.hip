@@ -740,6 +740,16 @@ int vimz_cf_kzg_open(vimz_cf* v, int which, const uint64_t z[4], uint64_t eval_o
   return which == 0 ? vz_kzg_open_device(ctx, p->ck, 0, VIMZ_FIELD_BN254_FR, p->Zrun + 8, p->n_wires - 3, z, VIMZ_FORM_CANONICAL, eval_out, proof_xy)
                     : vz_kzg_open_device(ctx, p->ck, 0, VIMZ_FIELD_BN254_FR, p->E, p->n_c, z, VIMZ_FORM_CANONICAL, eval_out, proof_xy);
 }
+// ... and the multilinear openings of the same two vectors (mlkzg.hip): the vector zero-padded to 2^logn, logn the least that holds it
+int vimz_cf_mlkzg_open(vimz_cf* v, int which, const uint64_t* point, uint32_t logn, uint64_t comm_out[8], uint64_t eval_out[4], uint64_t* proof, size_t cap_words,
+                       double seconds[4]) {
+  if (!v || !point || !comm_out || !eval_out || !proof || (which != 0 && which != 1)) return VIMZ_ERR_INVALID;
+  vimz_ctx* ctx = v->ctx; vimz_prover* p = v->pri;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  P_TRY(hipSetDevice(ctx->device));
+  return which == 0 ? vz_mlkzg_open_exact(ctx, p->ck, p->Zrun + 8, p->n_wires - 3, logn, point, comm_out, eval_out, proof, cap_words, seconds)
+                    : vz_mlkzg_open_exact(ctx, p->ck, p->E, p->n_c, logn, point, comm_out, eval_out, proof, cap_words, seconds);
+}
 
 #ifdef VIMZ_TESTING      // ---- test hooks: only in libvimz_hip_testing.so (include/vimz_hip_testing.h) ----
 // test hook: overwrite one element of a witness vector on the device (soundness tests flip wires and expect vimz_cf_verify / the

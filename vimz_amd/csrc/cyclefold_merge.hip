@@ -738,6 +738,17 @@ int vimz_cf_merged_kzg_open(vimz_cf_merged* m, int which, const uint64_t z[4], u
   return which == 0 ? vz_kzg_open_device(ctx, p->ck, 0, VIMZ_FIELD_BN254_FR, m->Zp + 8, p->n_wires - 3, z, VIMZ_FORM_CANONICAL, eval_out, proof_xy)
                     : vz_kzg_open_device(ctx, p->ck, 0, VIMZ_FIELD_BN254_FR, m->Ep, p->n_c, z, VIMZ_FORM_CANONICAL, eval_out, proof_xy);
 }
+// ... and their multilinear openings (vimz_cf_mlkzg_open for a merged proof)
+int vimz_cf_merged_mlkzg_open(vimz_cf_merged* m, int which, const uint64_t* point, uint32_t logn, uint64_t comm_out[8], uint64_t eval_out[4], uint64_t* proof,
+                              size_t cap_words, double seconds[4]) {
+  if (!m || !m->vk || !point || !comm_out || !eval_out || !proof || (which != 0 && which != 1)) return VIMZ_ERR_INVALID;
+  vimz_ctx* ctx = m->vk->ctx; vimz_prover* p = m->vk->pri;
+  if (m->broken) return vz_fail(ctx, VIMZ_ERR_INVALID, "vimz_cf_merged_mlkzg_open: this object failed in the middle of a merge");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  P_TRY(hipSetDevice(ctx->device));
+  return which == 0 ? vz_mlkzg_open_exact(ctx, p->ck, m->Zp + 8, p->n_wires - 3, logn, point, comm_out, eval_out, proof, cap_words, seconds)
+                    : vz_mlkzg_open_exact(ctx, p->ck, m->Ep, p->n_c, logn, point, comm_out, eval_out, proof, cap_words, seconds);
+}
 }  // extern "C"
 
 // ---- what spartan.hip needs of this file for the compressed merged proof (cyclefold_merge_internal.hpp) ---------------------------------------

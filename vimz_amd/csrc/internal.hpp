@@ -82,4 +82,11 @@ int vz_msm_device(vimz_ctx* c, const vimz_bases* bases, size_t base_offset, cons
 // KZG opening (vimz_kzg_open) of a device-resident vector of Montgomery elements of field `field` (caller holds c->mu and has set the device)
 int vz_kzg_open_device(vimz_ctx* c, const vimz_bases* srs, size_t base_offset, int field, const uint32_t* d_vec, size_t n, const uint64_t z[4], int form,
                        uint64_t eval_out[4], uint64_t proof_xy[8]);
+// Multilinear KZG opening (vimz_mlkzg_open, mlkzg.hip) of a device-resident vector of n <= 2^logn Montgomery elements of field `field` over the first 2^logn
+// powers of `srs` (caller holds c->mu and has set the device); point, the outputs and the proof canonical.  Takes its device buffers and frees them on every path.
+int vz_mlkzg_open_device(vimz_ctx* c, const vimz_bases* srs, int field, const uint32_t* d_vec, size_t n, uint32_t logn, const uint64_t* point, uint64_t comm_out[8],
+                         uint64_t eval_out[4], uint64_t* proof, size_t cap_words, double seconds[4]);
+// ... for a vector whose logn the caller does not choose (vimz_cf_mlkzg_open): refused unless logn is the least with 2^logn >= n
+int vz_mlkzg_open_exact(vimz_ctx* c, const vimz_bases* srs, const uint32_t* d_vec, size_t n, uint32_t logn, const uint64_t* point, uint64_t comm_out[8],
+                        uint64_t eval_out[4], uint64_t* proof, size_t cap_words, double seconds[4]);
 }

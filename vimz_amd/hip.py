@@ -340,6 +340,14 @@ class Context:
         ints = lambda a: sum(int(a[k]) << (64 * k) for k in range(4))
         return ints(ev), (ints(pr[:4]), ints(pr[4:]))
 
+    def mlkzg_open(self, srs, vec, point, n=None, offset=0, seconds=None):
+        """vimz_mlkzg_open: (comm as 8 words, eval as an integer, proof as 20·logn + 16 words) of vec[offset : offset + n] read as a multilinear polynomial in
+        len(point) variables, over the SRS powers `srs`.  seconds: a dict that receives the four phases."""
+        n = vec.n - offset if n is None else n
+        lib = self.lib
+        lib.vimz_mlkzg_open.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32] + _MLKZG_TAIL
+        return _mlkzg_open(self, lib.vimz_mlkzg_open, (self.h, srs.h, vec.h, offset, n, len(point)), point, seconds)
+
     # ---- probes
     def field_op(self, field, op, a, b=None):
         a = _u64(a)
@@ -804,6 +812,13 @@ class CycleFoldIVC:
         self.ctx._chk(lib.vimz_cf_kzg_open(self.h, which, _ptr(_zlimbs([z], 1)), _ptr(ev), _ptr(pr)))
         ints = lambda a: sum(int(a[k]) << (64 * k) for k in range(4))
         return ints(ev), (ints(pr[:4]), ints(pr[4:]))
+
+    def mlkzg_open(self, which, point, seconds=None):
+        """vimz_cf_mlkzg_open: (comm, eval, proof) as Context.mlkzg_open gives them for the running main instance's comm_W (which = 0) or comm_E (1); len(point) must
+        be the least logn with 2^logn >= the vector's length."""
+        lib = self.ctx.lib
+        lib.vimz_cf_mlkzg_open.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32] + _MLKZG_TAIL[1:]
+        return _mlkzg_open(self.ctx, lib.vimz_cf_mlkzg_open, (self.h, which), point, seconds, point_first=True)
 
     def digest_stride(self):
         lib = self.ctx.lib
@@ -1569,6 +1584,45 @@ def decider_verify_key(key_words, steps, z0, z_i, words):
     return int(res.value)
 
 
+MLKZG_PROBLEMS = {0x1: "malformed: word count, logn, an element not below r or a coordinate not below q", 0x2: "a point is not on its curve",
+                  0x4: "a fold equation between the evaluations fails", 0x8: "the pairing equation fails"}      # VIMZ_MLKZG_*
+MLKZG_PHASES = ("folds", "evaluations", "divisions", "quotient_commitments")
+_MLKZG_TAIL = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double)]      # point, comm_out, eval_out, proof, cap_words, seconds
+
+
+def _mlkzg_open(ctx, fn, head, point, seconds, point_first=False):
+    """the common tail of the three vimz_*mlkzg_open entries: head, then (point, logn) or (logn — the last of head —, point), then the outputs"""
+    logn = len(point)
+    lib = ctx.lib
+    lib.vimz_mlkzg_proof_words.argtypes, lib.vimz_mlkzg_proof_words.restype = [C.c_uint32], C.c_size_t
+    pt = _zlimbs([int(x) for x in point], max(logn, 1))
+    comm, ev = np.zeros(8, dtype=np.uint64), np.zeros(4, dtype=np.uint64)
+    proof = np.zeros(max(1, lib.vimz_mlkzg_proof_words(logn)), dtype=np.uint64)
+    sec = (C.c_double * 4)()
+    args = tuple(head) + (_ptr(pt), logn) if point_first else tuple(head) + (_ptr(pt),)
+    ctx._chk(fn(*args, _ptr(comm), _ptr(ev), _ptr(proof), lib.vimz_mlkzg_proof_words(logn), sec))
+    if seconds is not None:
+        seconds.update(zip(MLKZG_PHASES, list(sec)))
+    return comm, sum(int(ev[k]) << (64 * k) for k in range(4)), proof
+
+
+def mlkzg_verify(vk_g2, comm, point, eval, proof):
+    """vimz_mlkzg_verify: host only, no context, no GPU.  vk_g2: [tau]G2 as kzg_setup returns it; comm: 8 words; point: integers; eval: an integer; proof: words.
+    Returns the verdict word (0 = accepted, else one key of MLKZG_PROBLEMS)."""
+    lib = L.lib()
+    vp = C.c_void_p
+    lib.vimz_mlkzg_verify.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, C.c_size_t, C.POINTER(C.c_uint32)]
+    vk, cm, pr = _u64(vk_g2).reshape(-1), _u64(comm).reshape(-1), _u64(proof).reshape(-1)
+    if vk.size != 16 or cm.size != 8 or len(point) == 0:
+        raise L.VimzError(L.ERR_INVALID, "mlkzg_verify: vk_g2 has 16 words, comm 8, the point one element at least")
+    pt, ev = _zlimbs([int(x) for x in point], len(point)), _zlimbs([int(eval)], 1)
+    res = C.c_uint32(0)
+    rc = lib.vimz_mlkzg_verify(_ptr(vk), _ptr(cm), len(point), _ptr(pt), _ptr(ev), _ptr(pr), pr.size, C.byref(res))
+    if rc:
+        raise L.VimzError(rc, "vimz_mlkzg_verify: bad argument")
+    return int(res.value)
+
+
 BATCH_NO_BISECT = 1          # VIMZ_BATCH_NO_BISECT
 BATCH_STATS = ("chunks_refused", "subset_equations", "single_verifications", "accepted_by_subset")
 
@@ -1803,6 +1857,12 @@ class CycleFoldMerged:
         self.ctx._chk(lib.vimz_cf_merged_kzg_open(self.h, which, _ptr(_zlimbs([z], 1)), _ptr(ev), _ptr(pr)))
         ints = lambda a: sum(int(a[k]) << (64 * k) for k in range(4))
         return ints(ev), (ints(pr[:4]), ints(pr[4:]))
+
+    def mlkzg_open(self, which, point, seconds=None):
+        """vimz_cf_merged_mlkzg_open: CycleFoldIVC.mlkzg_open for the folded main instance."""
+        lib = self.ctx.lib
+        lib.vimz_cf_merged_mlkzg_open.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32] + _MLKZG_TAIL[1:]
+        return _mlkzg_open(self.ctx, lib.vimz_cf_merged_mlkzg_open, (self.h, which), point, seconds, point_first=True)
 
     def compress(self):
         """vimz_cf_merged_compress: the records and one argument each for the folded main and CycleFold instance.
